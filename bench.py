@@ -13,11 +13,26 @@ over xGMI (RCCL inside libmgx_analytics; torch.distributed gloo is used
 ONLY to bootstrap the ncclUniqueId and for wall-clock barriers — no torch
 in the compute path). Scaling is "strong": fixed RMAT-26 total work.
 
-cpu_baseline: the reference's own ParallelIterativePageRank compiled from
-/root/reference sources (oracle/_ref, kind "reference"; falls back to the
-oracle restatement, kind "port", if _ref wasn't built), timed on the host
-cores on a bounded sample (default RMAT-22, 6 iterations, nproc threads),
-scaled to edges/s. Rank 0, N=1 only.
+A plain run (`--gpus 1 --steps N --warmup W`) does only what the headline
+figure needs: build the graph, warm up, time the N sweeps, print the result
+line. Everything else the benchmark can measure or check sits behind
+`--full` (off by default): the CPU baseline, the `--check` parity run
+against the oracle, and the throwaway graph build that primes the allocator
+so that `csr_build_ms` is the steady-state COO->CSR time (without it
+`csr_build_ms` is the cold first build).
+
+--dump-outputs DIR: after the timed steps, write what a caller of the timed
+path receives after its last step, the normalized rank vector, as
+DIR/rank.npy (float64). Above DUMP_MAX_ELEMS vertices a fixed seeded sample
+of rows is written instead, so that two builds run with the same arguments
+can be compared output for output.
+
+cpu_baseline (--full): the reference's own ParallelIterativePageRank
+compiled from the reference sources (oracle/_ref, kind "reference"; falls
+back to the oracle restatement, kind "port", if _ref wasn't built), timed on
+the host cores on a bounded sample (default RMAT-22, 6 iterations, one thread
+per core, or OMP_NUM_THREADS where that is set lower), scaled to edges/s.
+Rank 0, N=1 only.
 
 roofline: dominant kernel = the fused SpMV sweep; algorithmic bytes per
 launch = E*8 + V*20; achieved = bytes / avg sweep launch time
@@ -35,6 +50,8 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
 
 HBM_PEAK = 8.0e12  # B/s, MI355X spec (MI355X_MICROARCH.md)
+DUMP_MAX_ELEMS = 1 << 22  # rows written by --dump-outputs (f64: 32 MiB)
+DUMP_SAMPLE_SEED = 20240229
 
 
 def parse_args():
@@ -46,11 +63,20 @@ def parse_args():
     p.add_argument("--edge-factor", type=int, default=16)
     p.add_argument("--damping", type=float, default=0.85)
     p.add_argument("--seed", type=int, default=1)
-    p.add_argument("--cpu-baseline", type=int, default=1)
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beyond the headline figure: the CPU "
+                        "baseline, --check, and the allocator-priming throwaway "
+                        "graph build behind the steady-state csr_build_ms")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the rank vector the timed path produced in its "
+                        "last step to DIR/rank.npy (seeded row sample when large)")
+    p.add_argument("--cpu-baseline", type=int, default=1,
+                   help="with --full: time the CPU baseline leg (0 turns it off)")
     p.add_argument("--cpu-sample-scale", type=int, default=22)
     p.add_argument("--cpu-sample-iters", type=int, default=6)
     p.add_argument("--check", type=int, default=0,
-                   help="verify the first steps against the oracle (small scales)")
+                   help="with --full: verify the first steps against the oracle "
+                        "(small scales)")
     p.add_argument("--algo", default="pagerank",
                    choices=["pagerank", "wcc", "katz", "louvain"],
                    help="pagerank is the contract workload; the others are "
@@ -62,7 +88,10 @@ def parse_args():
                         "divergent-gamma regime converges in one sweep)")
     p.add_argument("--katz-alpha", type=float, default=0.2)
     p.add_argument("--katz-eps", type=float, default=1e-2)
-    return p.parse_args()
+    args = p.parse_args()
+    if args.check and not args.full:
+        p.error("--check is part of the full run: pass --full with it")
+    return args
 
 
 def run_secondary(args):
@@ -148,6 +177,9 @@ def cpu_baseline_leg(args):
     n_edges = args.edge_factor * (1 << scale)
     src, dst = rmat.gen_rmat(scale, n_edges, seed=args.seed)
     cores = os.cpu_count() or 1
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and 0 < int(omp) < cores:
+        cores = int(omp)
     kind = None
     try:
         from oracle import Reference
@@ -180,6 +212,20 @@ def read_traffic(workload):
         data = json.load(f)
     entry = data.get(workload)
     return entry.get("bytes_per_launch") if entry else None
+
+
+def dump_outputs(outdir, rank_vec):
+    """DIR/rank.npy: the whole rank vector, or above DUMP_MAX_ELEMS rows a
+    sample at fixed seeded row indices (sorted, distinct)."""
+    import numpy as np
+    n = len(rank_vec)
+    if n > DUMP_MAX_ELEMS:
+        rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+        idx = np.unique(rng.integers(0, n, size=DUMP_MAX_ELEMS))
+        rank_vec = rank_vec[idx]
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "rank.npy"),
+            np.ascontiguousarray(rank_vec, dtype=np.float64))
 
 
 def main():
@@ -221,12 +267,13 @@ def main():
         g = nat.graph_rmat_sharded(ctx, args.scale, E, row_begin, row_end, seed=args.seed)
         run = nat.pagerank_start_dist(ctx, g, row_begin, row_end, damping=args.damping)
     else:
-        # Warm build: the first large hipMallocs stall the stream inside the
-        # build's event bracket (observed 0.3-1.7 s spread); a throwaway
-        # build primes the allocator so the reported CSR-build time is the
-        # actual device COO->CSR work.
-        g = nat.graph_rmat(ctx, args.scale, E, seed=args.seed, flags=BUILD_IN_CSR)
-        nat.graph_destroy(ctx, g)
+        # Warm build (--full): the first large hipMallocs stall the stream
+        # inside the build's event bracket (observed 0.3-1.7 s spread); a
+        # throwaway build primes the allocator so the reported CSR-build
+        # time is the actual device COO->CSR work.
+        if args.full:
+            g = nat.graph_rmat(ctx, args.scale, E, seed=args.seed, flags=BUILD_IN_CSR)
+            nat.graph_destroy(ctx, g)
         g = nat.graph_rmat(ctx, args.scale, E, seed=args.seed, flags=BUILD_IN_CSR)
         run = nat.pagerank_start(ctx, g, damping=args.damping)
     csr_build_ms = nat.graph_build_ms(g)
@@ -258,19 +305,23 @@ def main():
     sweep_launches = launches1 - launches0
     sweep_ms_avg = (sweep_ms1 - sweep_ms0) / max(sweep_launches, 1)
 
+    # The rank vector leaves the device only where something reads it.
+    check = args.full and args.check and rank == 0 and n_gpus == 1
+    dump = args.dump_outputs is not None and rank == 0
+    got = nat.pagerank_finish(run, V, want_rank=check or dump)
+    if dump:
+        dump_outputs(args.dump_outputs, got)
+
     check_note = None
-    if args.check and rank == 0 and n_gpus == 1:
+    if check:
         import numpy as np
         from oracle import Oracle
-        got = nat.pagerank_finish(run, V)
         orc = Oracle()
         src, dst = orc.gen_rmat(args.scale, E, seed=args.seed)
         exp, _ = orc.pagerank(V, src, dst, max_iterations=args.warmup + args.steps,
                               eps=0.0)
         check_note = float(np.abs(got - exp).max())
         assert check_note <= 1e-6, f"parity check failed: {check_note}"
-    else:
-        nat.pagerank_finish(run, want_rank=False)
 
     value = E * args.steps / elapsed  # whole-job edges/s, all ranks
 
@@ -319,7 +370,7 @@ def main():
         },
     }
     if rank == 0:
-        if n_gpus == 1 and args.cpu_baseline:
+        if args.full and n_gpus == 1 and args.cpu_baseline:
             result["cpu_baseline"] = cpu_baseline_leg(args)
         else:
             result["cpu_baseline"] = None

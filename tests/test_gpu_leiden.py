@@ -5,9 +5,10 @@ MoveNodesFast and minstd draws in MergeNodesSubset), so parity follows the
 DESIGN.md statistical bar: partition equality (canonicalized, per level) on
 trajectory-stable golden graphs where repeated reference runs agree, and
 partition QUALITY (CPM objective, community counts) within the reference's
-run distribution elsewhere. The reference core compiled from
-/root/reference (oracle/_ref/libref_online.so, ref_leiden) provides the
-comparison runs."""
+run distribution elsewhere. The reference core (ref_leiden in
+oracle/_ref/libref_online.so) provides the comparison runs; they are
+recorded in tests/golden/leiden_reference.json (tests/golden_replay.py says
+how to re-record), so the tests run where oracle/_ref cannot be built."""
 import ctypes
 import os
 import sys
@@ -20,6 +21,9 @@ sys.path.insert(0, REPO)
 
 from memgraph_amd.native import BUILD_SYM_CSR, BUILD_WEIGHTED, Native  # noqa: E402
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from golden_replay import GoldenReplay  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 I64 = ctypes.c_int64
@@ -29,10 +33,14 @@ CAP = 16
 
 
 class RefLeiden:
+    """The reference core: recorded runs, or the live library when
+    re-recording them."""
+
     def __init__(self):
+        self.golden = GoldenReplay("leiden_reference")
+        if not self.golden.recording:
+            return
         path = os.path.join(REPO, "oracle", "_ref", "libref_online.so")
-        if not os.path.exists(path):
-            pytest.skip("_ref online lib not built")
         self.lib = ctypes.CDLL(path)
         self.lib.ref_leiden.argtypes = [I64, I64, P64, P64, PD, ctypes.c_double,
                                         ctypes.c_double, ctypes.c_double, I64, I64,
@@ -40,6 +48,12 @@ class RefLeiden:
 
     def run(self, V, src, dst, weights=None, gamma=1.0, theta=0.01, resolution=0.01,
             max_iterations=(1 << 62)):
+        args = dict(V=V, src=src, dst=dst, weights=weights, gamma=gamma, theta=theta,
+                    resolution=resolution, max_iterations=max_iterations)
+        hier, lv = self.golden.call({"run": args, "cap": CAP}, lambda: self._run(**args))
+        return np.asarray(hier, dtype=np.int64), np.asarray(lv, dtype=np.int64)
+
+    def _run(self, V, src, dst, weights, gamma, theta, resolution, max_iterations):
         src = np.ascontiguousarray(src, dtype=np.int64)
         dst = np.ascontiguousarray(dst, dtype=np.int64)
         w = np.ascontiguousarray(weights if weights is not None else [],
@@ -69,6 +83,11 @@ def ctx(nat):
     nat.destroy(c)
 
 
+@pytest.fixture(scope="module")
+def ref():
+    return RefLeiden()
+
+
 def canonical_partition(labels):
     """labels -> canonical tuple (first-occurrence renumbering)."""
     remap = {}
@@ -90,10 +109,9 @@ SRC6 = [0, 1, 2, 3, 4, 5, 2]
 DST6 = [1, 2, 0, 4, 5, 3, 3]
 
 
-def test_leiden_golden_partition(nat, ctx):
+def test_leiden_golden_partition(nat, ctx, ref):
     """On the golden graph the reference's partition is trajectory-stable
     across its own random runs; ours must equal it (canonicalized)."""
-    ref = RefLeiden()
     parts = set()
     for _ in range(8):
         h, lv = ref.run(V6, SRC6, DST6)
@@ -135,7 +153,7 @@ def _cpm_quality(V, src, dst, labels, gamma_norm):
     return intra - gamma_norm * pen
 
 
-def test_leiden_quality_random(nat, ctx):
+def test_leiden_quality_random(nat, ctx, ref):
     """Planted-partition graph (8 dense clusters, sparse bridges): CPM finds
     the planted structure robustly in both implementations, so community
     count and CPM quality must sit inside the reference's run spread. A
@@ -162,7 +180,6 @@ def test_leiden_quality_random(nat, ctx):
     uniq = {(min(s, d), max(s, d)) for s, d in zip(src, dst)}
     gamma_norm = 1.0 / sum(1.0 for _ in uniq)
 
-    ref = RefLeiden()
     ref_q = []
     ref_k = []
     for _ in range(10):
@@ -187,10 +204,9 @@ def test_leiden_quality_random(nat, ctx):
     nat.graph_destroy(ctx, g)
 
 
-def test_leiden_weighted(nat, ctx):
+def test_leiden_weighted(nat, ctx, ref):
     """Weighted golden: heavier triangle edges dominate the bridge."""
     w = [5.0, 5.0, 5.0, 5.0, 5.0, 5.0, 0.5]
-    ref = RefLeiden()
     h, lv = ref.run(V6, SRC6, DST6, weights=w)
     if (lv < 0).any():
         pytest.skip("reference errored on the weighted golden run")

@@ -1,10 +1,11 @@
 """GPU tests for community_detection_online / LabelRankT.
 
 LabelRankT is deterministic (no RNG), so the parity bar is EXACT label
-equality against the reference's own LabelRankT core compiled from
-/root/reference into oracle/_ref/libref_online.so — the binary travels to
-the GPU box (oracle/_ref is git-ignored but not gpurun-ignored), and for
-this row the compiled reference IS the oracle."""
+equality against the reference's own LabelRankT core (ref_lrt_* in
+oracle/_ref/libref_online.so) — for this row the compiled reference IS the
+oracle. Its outputs for the calls below are recorded in
+tests/golden/lrt_reference.json (tests/golden_replay.py says how to
+re-record), so the tests run where oracle/_ref cannot be built."""
 import ctypes
 import os
 import sys
@@ -18,6 +19,9 @@ sys.path.insert(0, REPO)
 from memgraph_amd.native import (BUILD_IN_CSR, BUILD_NO_PERM, BUILD_SYM_CSR,
                                  BUILD_WEIGHTED, Native)  # noqa: E402
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from golden_replay import GoldenReplay  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 I64 = ctypes.c_int64
@@ -26,10 +30,14 @@ PD = ctypes.POINTER(ctypes.c_double)
 
 
 class RefLrt:
+    """The reference core: recorded outputs, or the live library when
+    re-recording them."""
+
     def __init__(self):
+        self.golden = GoldenReplay("lrt_reference")
+        if not self.golden.recording:
+            return
         path = os.path.join(REPO, "oracle", "_ref", "libref_online.so")
-        if not os.path.exists(path):
-            pytest.skip("_ref online lib not built")
         self.lib = ctypes.CDLL(path)
         self.lib.ref_lrt_set.argtypes = [
             I64, P64, I64, P64, P64, PD, ctypes.c_int32, ctypes.c_int32,
@@ -47,6 +55,15 @@ class RefLrt:
     def set(self, nodes, src, dst, weights=None, directed=False, weighted=False,
             sim_th=0.7, exponent=4.0, min_value=0.1, w_selfloop=1.0,
             max_iterations=100, max_updates=5):
+        args = dict(nodes=nodes, src=src, dst=dst, weights=weights, directed=directed,
+                    weighted=weighted, sim_th=sim_th, exponent=exponent,
+                    min_value=min_value, w_selfloop=w_selfloop,
+                    max_iterations=max_iterations, max_updates=max_updates)
+        out = self.golden.call({"set": args}, lambda: self._set(**args))
+        return np.asarray(out, dtype=np.int64)
+
+    def _set(self, nodes, src, dst, weights, directed, weighted, sim_th, exponent,
+             min_value, w_selfloop, max_iterations, max_updates):
         nodes = self.arr(nodes)
         src = self.arr(src)
         dst = self.arr(dst)
@@ -63,6 +80,12 @@ class RefLrt:
 
     def update(self, nodes, src, dst, weights=None, directed=False, mv=(), me=(),
                dv=(), de=()):
+        args = dict(nodes=nodes, src=src, dst=dst, weights=weights, directed=directed,
+                    mv=mv, me=me, dv=dv, de=de)
+        out = self.golden.call({"update": args}, lambda: self._update(**args))
+        return np.asarray(out, dtype=np.int64)
+
+    def _update(self, nodes, src, dst, weights, directed, mv, me, dv, de):
         nodes = self.arr(nodes)
         src = self.arr(src)
         dst = self.arr(dst)
@@ -83,7 +106,8 @@ class RefLrt:
         return out
 
     def reset(self):
-        self.lib.ref_lrt_reset()
+        if self.golden.recording:
+            self.lib.ref_lrt_reset()
 
 
 @pytest.fixture(scope="module")
@@ -101,12 +125,16 @@ def ctx(nat):
     nat.destroy(c)
 
 
+@pytest.fixture(scope="module")
+def ref_lrt():
+    return RefLrt()
+
+
 @pytest.fixture
-def ref():
-    r = RefLrt()
-    r.reset()
-    yield r
-    r.reset()
+def ref(ref_lrt):
+    ref_lrt.reset()
+    yield ref_lrt
+    ref_lrt.reset()
 
 
 def make_graph(nat, ctx, V, src, dst, weights=None, directed=False):
