@@ -13,7 +13,7 @@ MGX_HIP_SRCS := memgraph_amd/csrc/graph_build.hip memgraph_amd/csrc/pagerank.hip
                 memgraph_amd/csrc/pronline.hip memgraph_amd/csrc/katz_online.hip \
                 memgraph_amd/csrc/labelrankt.hip memgraph_amd/csrc/leiden.hip \
                 memgraph_amd/csrc/wcc.hip memgraph_amd/csrc/katz.hip \
-                memgraph_amd/csrc/betweenness.hip \
+                memgraph_amd/csrc/betweenness.hip memgraph_amd/csrc/bfs.hip \
                 memgraph_amd/csrc/louvain.hip
 MGX_OBJS := $(MGX_SRCS:%.cpp=build/%.o) $(MGX_HIP_SRCS:%.hip=build/%.o)
 

@@ -147,6 +147,37 @@ mgx_status mgx_pagerank_finish(mgx_pagerank_run *run, double *out_rank /* nullab
 mgx_status mgx_wcc(mgx_context *ctx, mgx_graph *g, int64_t *out_component,
                    int64_t *n_components);
 
+/* ---- Single-source BFS: hop counts and parents (replaces the queue BFS of
+ *      connectivity_module.cpp:50-71 for the undirected level structure,
+ *      and the level sets of neighbors.at_hop / neighbors.by_hop,
+ *      src/mage/cpp/neighbors_module/algorithm/neighbors.cpp:52-160: hop l
+ *      of the reference is {v : out_hops[v] == l}, `distance` is max_depth,
+ *      and the typed/directed rule of neighbors.cpp:26-48 is applied by the
+ *      caller when it builds the traversal COO) ---------------------------
+ * Direction-optimizing (Beamer): top-down over degree-binned frontier
+ * queues, bottom-up over the symmetric CSR against a frontier bitmap;
+ * MGX_BFS_ALPHA / MGX_BFS_BETA (defaults 14 / 24) override the switch.
+ * source is an original vertex id. directed=1 needs MGX_BUILD_OUT_CSR and
+ * follows from->to (top-down only); directed=0 needs MGX_BUILD_SYM_CSR.
+ * out_hops[v] = hop count, 0 for the source, -1 if unreachable or beyond
+ * max_depth. out_parent[v] = the minimum-id neighbour at hops-1,
+ * parent[source] = source, -1 where hops is -1. Both deterministic. */
+#define MGX_BFS_AUTO 0
+#define MGX_BFS_TOP_DOWN 1
+#define MGX_BFS_BOTTOM_UP 2 /* every level bottom-up; undirected only */
+typedef struct {
+  int64_t depth;           /* deepest hop reached */
+  int64_t reached;         /* vertices with hops >= 0 */
+  int64_t entries_scanned; /* CSR entries examined */
+  int64_t top_down_levels, bottom_up_levels;
+  uint64_t bottom_up_mask; /* bit l set <=> level l expanded bottom-up (l < 64) */
+  double ms;               /* HIP-event time, excluding download */
+} mgx_bfs_stats;
+mgx_status mgx_bfs(mgx_context *ctx, mgx_graph *g, int64_t source, int directed,
+                   int64_t max_depth /* <0 = unlimited */, int mode,
+                   int64_t *out_hops /* nullable */, int64_t *out_parent /* nullable */,
+                   mgx_bfs_stats *stats /* nullable */);
+
 /* ---- Katz (replaces katz_alg::SetKatz, katz.cpp:393-414) ---------------
  * Needs IN_CSR. Convergence rule replicates Converged (katz.cpp:165-215)
  * after the k-override, incl. divergent-series IEEE behavior. */

@@ -382,6 +382,13 @@ extern "C" mgx_status mgx_wcc(mgx_context *ctx, mgx_graph *g, int64_t *out_compo
   return mgx_wcc_impl(ctx, g, out_component, n_components);
 }
 
+extern "C" mgx_status mgx_bfs(mgx_context *ctx, mgx_graph *g, int64_t source, int directed,
+                              int64_t max_depth, int mode, int64_t *out_hops,
+                              int64_t *out_parent, mgx_bfs_stats *stats) {
+  MGX_HIP_TRY(hipSetDevice(ctx->device));
+  return mgx_bfs_impl(ctx, g, source, directed, max_depth, mode, out_hops, out_parent, stats);
+}
+
 extern "C" mgx_status mgx_katz(mgx_context *ctx, mgx_graph *g, double alpha, double epsilon,
                                double *out_centrality, int64_t *iterations) {
   MGX_HIP_TRY(hipSetDevice(ctx->device));

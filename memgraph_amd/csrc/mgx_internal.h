@@ -240,6 +240,11 @@ mgx_status mgx_louvain_impl(mgx_context *ctx, mgx_graph *g, double threshold,
 mgx_status mgx_betweenness_impl(mgx_context *ctx, mgx_graph *g, int directed, int normalize,
                                 double *out_bc);
 
+// bfs.hip
+mgx_status mgx_bfs_impl(mgx_context *ctx, mgx_graph *g, int64_t source, int directed,
+                        int64_t max_depth, int mode, int64_t *out_hops, int64_t *out_parent,
+                        mgx_bfs_stats *stats);
+
 // comm.cpp (RCCL)
 mgx_status mgx_comm_allgather_f32(mgx_context *ctx, const float *send, float *recv,
                                   size_t per_rank_count);

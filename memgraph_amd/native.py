@@ -34,6 +34,23 @@ class PagerankStats(ctypes.Structure):
     ]
 
 
+BFS_AUTO = 0
+BFS_TOP_DOWN = 1
+BFS_BOTTOM_UP = 2
+
+
+class BfsStats(ctypes.Structure):
+    _fields_ = [
+        ("depth", ctypes.c_int64),
+        ("reached", ctypes.c_int64),
+        ("entries_scanned", ctypes.c_int64),
+        ("top_down_levels", ctypes.c_int64),
+        ("bottom_up_levels", ctypes.c_int64),
+        ("bottom_up_mask", ctypes.c_uint64),
+        ("ms", ctypes.c_double),
+    ]
+
+
 class MgxError(RuntimeError):
     pass
 
@@ -175,6 +192,27 @@ class Native:
         self._check(self.lib.mgx_wcc(ctx, g, out.ctypes.data_as(_I64), ctypes.byref(n)),
                     "mgx_wcc")
         return out, n.value
+
+    def bfs_status(self, ctx, g, n_vertices, source, directed=False, max_depth=-1,
+                   mode=BFS_AUTO, want_parent=False):
+        """Raw call: (status, hops, parent_or_None, stats) without raising."""
+        hops = np.full(n_vertices, -1, dtype=np.int64)
+        parent = np.full(n_vertices, -1, dtype=np.int64) if want_parent else None
+        stats = BfsStats()
+        status = self.lib.mgx_bfs(ctx, g, ctypes.c_int64(source),
+                                  ctypes.c_int(1 if directed else 0),
+                                  ctypes.c_int64(max_depth), ctypes.c_int(mode),
+                                  hops.ctypes.data_as(_I64),
+                                  parent.ctypes.data_as(_I64) if want_parent else None,
+                                  ctypes.byref(stats))
+        return status, hops, parent, stats
+
+    def bfs(self, ctx, g, n_vertices, source, directed=False, max_depth=-1, mode=BFS_AUTO,
+            want_parent=False):
+        status, hops, parent, stats = self.bfs_status(ctx, g, n_vertices, source, directed,
+                                                      max_depth, mode, want_parent)
+        self._check(status, "mgx_bfs")
+        return hops, parent, stats
 
     def katz(self, ctx, g, n_vertices, alpha=0.2, epsilon=1e-2):
         out = np.zeros(n_vertices, dtype=np.float64)
