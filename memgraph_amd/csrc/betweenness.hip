@@ -21,17 +21,11 @@
 // duplicated adjacency entries do), dependencies halved
 // (betweenness_centrality.cpp:102).
 
-#include "mgx_internal.h"
+#include "mgx_device.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-
-inline int64_t grid_for(int64_t work, int64_t cap = 8192) {
-  int64_t g = (work + kBlock - 1) / kBlock;
-  if (g < 1) g = 1;
-  return g > cap ? cap : g;
-}
+constexpr int64_t kGridCap = 8192;  // element-wise launches of this file
 
 __global__ void k_bc_init_batch(int64_t n, int32_t *dist, unsigned long long *sigma,
                                 double *dep) {
@@ -152,15 +146,16 @@ mgx_status mgx_betweenness_impl(mgx_context *ctx, mgx_graph *g, int directed, in
 
   for (int64_t s0 = 0; s0 < V; s0 += batch) {
     const int64_t nb = (s0 + batch <= V) ? batch : (V - s0);
-    hipLaunchKernelGGL(k_bc_init_batch, dim3((uint32_t)grid_for(nb * V)), dim3(kBlock), 0,
+    const uint32_t grid_bv = (uint32_t)grid_for(nb * V, kGridCap);
+    hipLaunchKernelGGL(k_bc_init_batch, dim3(grid_bv), dim3(kBlock), 0,
                        ctx->stream, nb * V, dist, sigma, dep);
-    hipLaunchKernelGGL(k_bc_seed, dim3((uint32_t)grid_for(nb)), dim3(kBlock), 0,
+    hipLaunchKernelGGL(k_bc_seed, dim3((uint32_t)grid_for(nb, kGridCap)), dim3(kBlock), 0,
                        ctx->stream, nb, s0, V, dist, sigma);
     // forward BFS levels
     int32_t level = 0;
     while (true) {
       MGX_HIP_TRY(hipMemsetAsync(d_changed, 0, 4, ctx->stream));
-      hipLaunchKernelGGL(k_bc_forward, dim3((uint32_t)grid_for(nb * V)), dim3(kBlock), 0,
+      hipLaunchKernelGGL(k_bc_forward, dim3(grid_bv), dim3(kBlock), 0,
                          ctx->stream, nb, V, row_ptr, col, dist, sigma, level, d_changed);
       uint32_t h_changed = 0;
       MGX_HIP_TRY(hipMemcpyAsync(&h_changed, d_changed, 4, hipMemcpyDeviceToHost,
@@ -177,10 +172,10 @@ mgx_status mgx_betweenness_impl(mgx_context *ctx, mgx_graph *g, int directed, in
     // never emitted; level 0 pulls are still needed for dep of sources'
     // predecessors-of-successors — matching the reference's stack walk).
     for (int32_t l = level - 1; l >= 0; --l) {
-      hipLaunchKernelGGL(k_bc_backward, dim3((uint32_t)grid_for(nb * V)), dim3(kBlock), 0,
+      hipLaunchKernelGGL(k_bc_backward, dim3(grid_bv), dim3(kBlock), 0,
                          ctx->stream, nb, V, row_ptr, col, dist, sigma, dep, l);
     }
-    hipLaunchKernelGGL(k_bc_accumulate, dim3((uint32_t)grid_for(nb * V)), dim3(kBlock), 0,
+    hipLaunchKernelGGL(k_bc_accumulate, dim3(grid_bv), dim3(kBlock), 0,
                        ctx->stream, nb, s0, V, dist, dep, directed, bc);
   }
 
@@ -189,7 +184,7 @@ mgx_status mgx_betweenness_impl(mgx_context *ctx, mgx_graph *g, int directed, in
     const double pairs = (double)((V - 1) * (V - 2));
     const double numerator = directed ? 1.0 : 2.0;
     const double constant = V > 2 ? numerator / pairs : 1.0;
-    hipLaunchKernelGGL(k_bc_normalize, dim3((uint32_t)grid_for(V)), dim3(kBlock), 0,
+    hipLaunchKernelGGL(k_bc_normalize, dim3((uint32_t)grid_for(V, kGridCap)), dim3(kBlock), 0,
                        ctx->stream, V, constant, bc);
   }
   if (out_bc) {

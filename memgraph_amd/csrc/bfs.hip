@@ -41,17 +41,11 @@
 #include <climits>
 #include <cstdlib>
 
-#include "mgx_internal.h"
+#include "mgx_device.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-
-inline int64_t grid_for(int64_t work, int64_t cap = 2048) {
-  int64_t g = (work + kBlock - 1) / kBlock;
-  if (g < 1) g = 1;
-  return g > cap ? cap : g;
-}
+constexpr int64_t kGridCap = 2048;  // element-wise launches of this file
 
 struct BfsCounters {
   uint32_t tail[4];            // cumulative entries queued per degree class
@@ -184,19 +178,10 @@ __device__ inline void td_rows(const BfsTdArgs &A, int c, int64_t block_in_sec,
 }
 
 __global__ void __launch_bounds__(kBlock) k_bfs_top_down(BfsTdArgs A) {
-  const int64_t b = blockIdx.x;
-  int sec = 3;
-  if (b < A.goff[1]) sec = 0;
-  else if (b < A.goff[2]) sec = 1;
-  else if (b < A.goff[3]) sec = 2;
-  const int64_t bis = b - A.goff[sec];
   unsigned long long acc_deg = 0, acc_n = 0;
-  switch (sec) {
-    case 0: td_rows<4>(A, 0, bis, acc_deg, acc_n); break;
-    case 1: td_rows<16>(A, 1, bis, acc_deg, acc_n); break;
-    case 2: td_rows<64>(A, 2, bis, acc_deg, acc_n); break;
-    default: td_rows<256>(A, 3, bis, acc_deg, acc_n); break;
-  }
+  for_bin_section(A.goff, [&](auto lanes, int c, int64_t bis) {
+    td_rows<decltype(lanes)::value>(A, c, bis, acc_deg, acc_n);
+  });
   acc_deg = wave_sum(acc_deg);
   acc_n = wave_sum(acc_n);
   if ((threadIdx.x & 63) == 0 && acc_n) {
@@ -255,8 +240,7 @@ __global__ void k_bfs_bitmap_to_queue(int64_t V, const uint32_t *row_ptr, const 
 struct BfsBuArgs {
   const uint32_t *row_ptr;
   const int32_t *col;
-  const int32_t *bin_rows;
-  int64_t n[4], off[4], goff[4], grid[4];
+  mgx_bin_sections bins;
   uint32_t *visited;
   const uint32_t *fcur;
   uint32_t *fnext;
@@ -270,17 +254,10 @@ template <int LANES>
 __device__ inline void bu_rows(const BfsBuArgs &A, int sec, int64_t block_in_sec,
                                unsigned long long &acc_deg, unsigned long long &acc_n,
                                unsigned long long &acc_scan) {
-  constexpr int RPB = kBlock / LANES;
-  const int64_t nrows = A.n[sec];
-  const int32_t *rows_list = A.bin_rows + A.off[sec];
-  const int sub = threadIdx.x % LANES;
   const int lane = threadIdx.x & 63;
   __shared__ uint32_t s_hit[4];
-  for (int64_t base = block_in_sec * RPB; base < nrows; base += A.grid[sec] * RPB) {
-    const int64_t ri = base + threadIdx.x / LANES;
-    if (ri >= nrows) continue;
-    const int32_t row = rows_list[ri];
-    if ((A.visited[(uint32_t)row >> 5] >> (row & 31)) & 1u) continue;
+  for_bin_rows<LANES>(A.bins, sec, block_in_sec, [&](int32_t row, int sub) {
+    if ((A.visited[(uint32_t)row >> 5] >> (row & 31)) & 1u) return;
     const int64_t s = A.row_ptr[row], e = A.row_ptr[row + 1];
     // Everything below is uniform across the LANES lanes that share a row.
     // found = CSR index of the first hit (entries < 2^32 - 1).
@@ -326,23 +303,14 @@ __device__ inline void bu_rows(const BfsBuArgs &A, int sec, int64_t block_in_sec
         acc_n += 1;
       }
     }
-  }
+  });
 }
 
 __global__ void __launch_bounds__(kBlock) k_bfs_bottom_up(BfsBuArgs A) {
-  const int64_t b = blockIdx.x;
-  int sec = 3;
-  if (b < A.goff[1]) sec = 0;
-  else if (b < A.goff[2]) sec = 1;
-  else if (b < A.goff[3]) sec = 2;
-  const int64_t bis = b - A.goff[sec];
   unsigned long long acc_deg = 0, acc_n = 0, acc_scan = 0;
-  switch (sec) {
-    case 0: bu_rows<4>(A, 0, bis, acc_deg, acc_n, acc_scan); break;
-    case 1: bu_rows<16>(A, 1, bis, acc_deg, acc_n, acc_scan); break;
-    case 2: bu_rows<64>(A, 2, bis, acc_deg, acc_n, acc_scan); break;
-    default: bu_rows<256>(A, 3, bis, acc_deg, acc_n, acc_scan); break;
-  }
+  for_bin_section(A.bins.goff, [&](auto lanes, int sec, int64_t bis) {
+    bu_rows<decltype(lanes)::value>(A, sec, bis, acc_deg, acc_n, acc_scan);
+  });
   acc_deg = wave_sum(acc_deg);
   acc_n = wave_sum(acc_n);
   acc_scan = wave_sum(acc_scan);
@@ -430,8 +398,8 @@ mgx_status mgx_bfs_impl(mgx_context *ctx, mgx_graph *g, int64_t source, int dire
   MGX_HIP_TRY(hipMemsetAsync(fcur, 0, W * sizeof(uint32_t), ctx->stream));
   MGX_HIP_TRY(hipMemsetAsync(fnext, 0, W * sizeof(uint32_t), ctx->stream));
   MGX_HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(BfsCounters), ctx->stream));
-  hipLaunchKernelGGL(k_bfs_init, dim3((uint32_t)grid_for(V)), dim3(kBlock), 0, ctx->stream, V,
-                     hops, parent);
+  hipLaunchKernelGGL(k_bfs_init, dim3((uint32_t)grid_for(V, kGridCap)), dim3(kBlock), 0,
+                     ctx->stream, V, hops, parent);
   hipLaunchKernelGGL(k_bfs_seed, dim3(1), dim3(64), 0, ctx->stream, (int32_t)source, row_ptr,
                      hops, parent, visited, fcur, q01, q23, V, d_cnt);
 
@@ -469,8 +437,8 @@ mgx_status mgx_bfs_impl(mgx_context *ctx, mgx_graph *g, int64_t source, int dire
     if (!bottom_up) {
       if (!have_queue) {
         for (int c = 0; c < 4; ++c) q_start[c] = h.tail[c];
-        hipLaunchKernelGGL(k_bfs_bitmap_to_queue, dim3((uint32_t)grid_for(V)), dim3(kBlock), 0,
-                           ctx->stream, V, row_ptr, fcur, q01, q23, d_cnt);
+        hipLaunchKernelGGL(k_bfs_bitmap_to_queue, dim3((uint32_t)grid_for(V, kGridCap)),
+                           dim3(kBlock), 0, ctx->stream, V, row_ptr, fcur, q01, q23, d_cnt);
         MGX_TRY(read_counters(&h));
         for (int c = 0; c < 4; ++c) q_end[c] = h.tail[c];
         have_queue = true;
@@ -513,16 +481,7 @@ mgx_status mgx_bfs_impl(mgx_context *ctx, mgx_graph *g, int64_t source, int dire
       BfsBuArgs A;
       A.row_ptr = row_ptr;
       A.col = col;
-      A.bin_rows = g->bins_sym.rows;
-      int64_t off = 0, goff = 0;
-      for (int b = 0; b < 4; ++b) {
-        A.n[b] = g->bins_sym.count[b];
-        A.off[b] = off;
-        off += A.n[b];
-        A.goff[b] = goff;
-        A.grid[b] = g->bins_sym.grid[b];
-        goff += A.grid[b];
-      }
+      const int64_t goff = mgx_fill_sections(g->bins_sym, &A.bins);
       A.visited = visited;
       A.fcur = fcur;
       A.fnext = fnext;
@@ -558,7 +517,7 @@ mgx_status mgx_bfs_impl(mgx_context *ctx, mgx_graph *g, int64_t source, int dire
       }
       F.visited = visited;
       F.fold = fcur;
-      hipLaunchKernelGGL(k_bfs_td_finish, dim3((uint32_t)grid_for(work)), dim3(kBlock), 0,
+      hipLaunchKernelGGL(k_bfs_td_finish, dim3((uint32_t)grid_for(work, kGridCap)), dim3(kBlock), 0,
                          ctx->stream, F);
     }
     std::swap(fcur, fnext);
@@ -578,8 +537,8 @@ mgx_status mgx_bfs_impl(mgx_context *ctx, mgx_graph *g, int64_t source, int dire
   if (out_hops) MGX_TRY(ctx->alloc_async((void **)&d_out_hops, V * sizeof(int64_t)));
   if (out_parent) MGX_TRY(ctx->alloc_async((void **)&d_out_parent, V * sizeof(int64_t)));
   if (out_hops || out_parent) {
-    hipLaunchKernelGGL(k_bfs_emit, dim3((uint32_t)grid_for(V)), dim3(kBlock), 0, ctx->stream,
-                       V, hops, parent, d_out_hops, d_out_parent);
+    hipLaunchKernelGGL(k_bfs_emit, dim3((uint32_t)grid_for(V, kGridCap)), dim3(kBlock), 0,
+                       ctx->stream, V, hops, parent, d_out_hops, d_out_parent);
     if (out_hops)
       MGX_HIP_TRY(hipMemcpyAsync(out_hops, d_out_hops, V * sizeof(int64_t),
                                  hipMemcpyDeviceToHost, ctx->stream));

@@ -12,18 +12,9 @@
 #include <rocprim/rocprim.hpp>
 
 #include "../../include/mgx_graphgen.h"
-#include "mgx_internal.h"
+#include "mgx_device.h"
 
 namespace {
-
-constexpr int kBlock = 256;
-
-inline int64_t grid_for(int64_t work, int64_t cap = 4096) {
-  int64_t g = (work + kBlock - 1) / kBlock;
-  if (g < 1) g = 1;
-  if (g > cap) g = cap;
-  return g;
-}
 
 __global__ void k_rmat(int64_t n_edges, int scale, uint64_t mixed_seed,
                        mgx_rmat_thresholds t, int32_t *src, int32_t *dst) {
@@ -76,12 +67,6 @@ __global__ void k_hist_ranged(int64_t n_edges, const int32_t *idx, int32_t lo, i
     int32_t v = idx[i];
     if (v >= lo && v < hi) atomicAdd(&counts[v - lo], 1u);
   }
-}
-
-__global__ void k_iota_i32g(int64_t n, int32_t *p) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    p[i] = (int32_t)i;
 }
 
 __global__ void k_inv_outdeg(int64_t n, const uint32_t *deg, float *inv) {
@@ -185,15 +170,10 @@ mgx_status build_sorted_cols(mgx_context *ctx, const int32_t *d_src, const int32
   int end_bit = 33;
   while ((1ll << (end_bit - 32)) < key_rows + 1) ++end_bit;
   if (ranged) end_bit = 64;  // the ~0 sentinel must sort last
-  size_t tmp_bytes = 0;
-  auto err = rocprim::radix_sort_keys(nullptr, tmp_bytes, keys, keys_out, n_edges, 0,
-                                      end_bit, ctx->stream);
-  if (err != hipSuccess) return MGX_ERR_HIP;
-  void *tmp = nullptr;
-  MGX_TRY(ctx->reserve(tmp_bytes, &tmp));
-  err = rocprim::radix_sort_keys(tmp, tmp_bytes, keys, keys_out, n_edges, 0, end_bit,
-                                 ctx->stream);
-  if (err != hipSuccess) return MGX_ERR_HIP;
+  MGX_TRY(mgx_with_temp(ctx, "edge key sort", [&](void *tmp, size_t &bytes) {
+    return rocprim::radix_sort_keys(tmp, bytes, keys, keys_out, n_edges, 0, end_bit,
+                                    ctx->stream);
+  }));
   hipLaunchKernelGGL(k_unpack_cols, dim3(grid_for(col_count)), dim3(kBlock), 0, ctx->stream,
                      col_count, keys_out, col);
   MGX_TRY(ctx->free_async(keys));
@@ -219,16 +199,10 @@ mgx_status build_sorted_cols_w(mgx_context *ctx, const int32_t *d_src,
                      n_edges, d_src, d_dst, (const int32_t *)nullptr, keys);
   int end_bit = 33;
   while ((1ll << (end_bit - 32)) < key_rows + 1) ++end_bit;
-  size_t tmp_bytes = 0;
-  auto err = rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys, keys_out,
-                                       (const float *)d_w, vals_out, n_edges, 0, end_bit,
-                                       ctx->stream);
-  if (err != hipSuccess) return MGX_ERR_HIP;
-  void *tmp = nullptr;
-  MGX_TRY(ctx->reserve(tmp_bytes, &tmp));
-  err = rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, keys_out, (const float *)d_w,
-                                  vals_out, n_edges, 0, end_bit, ctx->stream);
-  if (err != hipSuccess) return MGX_ERR_HIP;
+  MGX_TRY(mgx_with_temp(ctx, "weighted edge sort", [&](void *tmp, size_t &bytes) {
+    return rocprim::radix_sort_pairs(tmp, bytes, keys, keys_out, (const float *)d_w,
+                                     vals_out, n_edges, 0, end_bit, ctx->stream);
+  }));
   hipLaunchKernelGGL(k_unpack_cols, dim3(grid_for(n_edges)), dim3(kBlock), 0, ctx->stream,
                      n_edges, keys_out, col);
   MGX_HIP_TRY(hipMemcpyAsync(out_w, vals_out, n_edges * sizeof(float),
@@ -274,26 +248,12 @@ mgx_status build_sorted_sym(mgx_context *ctx, const int32_t *d_src, const int32_
                      n_edges, d_src, d_dst, d_w, keys, vals);
   int end_bit = 33;
   while ((1ll << (end_bit - 32)) < n_vertices + 1) ++end_bit;
-  size_t tmp_bytes = 0;
-  hipError_t err;
-  if (out_w) {
-    err = rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys, keys_out, vals, vals_out, n2,
-                                    0, end_bit, ctx->stream);
-  } else {
-    err = rocprim::radix_sort_keys(nullptr, tmp_bytes, keys, keys_out, n2, 0, end_bit,
-                                   ctx->stream);
-  }
-  if (err != hipSuccess) return MGX_ERR_HIP;
-  void *tmp = nullptr;
-  MGX_TRY(ctx->reserve(tmp_bytes, &tmp));
-  if (out_w) {
-    err = rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, keys_out, vals, vals_out, n2, 0,
-                                    end_bit, ctx->stream);
-  } else {
-    err = rocprim::radix_sort_keys(tmp, tmp_bytes, keys, keys_out, n2, 0, end_bit,
-                                   ctx->stream);
-  }
-  if (err != hipSuccess) return MGX_ERR_HIP;
+  MGX_TRY(mgx_with_temp(ctx, "symmetric edge sort", [&](void *tmp, size_t &bytes) {
+    if (out_w)
+      return rocprim::radix_sort_pairs(tmp, bytes, keys, keys_out, vals, vals_out, n2, 0,
+                                       end_bit, ctx->stream);
+    return rocprim::radix_sort_keys(tmp, bytes, keys, keys_out, n2, 0, end_bit, ctx->stream);
+  }));
   hipLaunchKernelGGL(k_unpack_cols, dim3(grid_for(n2)), dim3(kBlock), 0, ctx->stream, n2,
                      keys_out, col);
   if (out_w) {
@@ -322,17 +282,12 @@ __global__ void k_f64_to_f32(int64_t n, const double *in, float *out) {
 // Exclusive scan of u32 counts[n] -> row_ptr[n+1] (row_ptr[n] = total).
 mgx_status scan_counts(mgx_context *ctx, const uint32_t *counts, int64_t n,
                        uint32_t *row_ptr) {
-  size_t tmp_bytes = 0;
-  auto err = rocprim::exclusive_scan(nullptr, tmp_bytes, counts, row_ptr, 0u, n + 1,
-                                     rocprim::plus<uint32_t>(), ctx->stream);
-  if (err != hipSuccess) return MGX_ERR_HIP;
-  void *tmp = nullptr;
-  MGX_TRY(ctx->reserve(tmp_bytes, &tmp));
-  // Scan n+1 inputs (counts has n entries; read one past would be invalid) —
-  // instead scan n entries into row_ptr[0..n) and set the total separately.
-  err = rocprim::exclusive_scan(tmp, tmp_bytes, counts, row_ptr, 0u, n,
-                                rocprim::plus<uint32_t>(), ctx->stream);
-  if (err != hipSuccess) return MGX_ERR_HIP;
+  // counts has n entries (reading one past would be invalid): scan n entries
+  // into row_ptr[0..n) and set the total separately.
+  MGX_TRY(mgx_with_temp(ctx, "row_ptr scan", [&](void *tmp, size_t &bytes) {
+    return rocprim::exclusive_scan(tmp, bytes, counts, row_ptr, 0u, n,
+                                   rocprim::plus<uint32_t>(), ctx->stream);
+  }));
   // row_ptr[n] = row_ptr[n-1] + counts[n-1]
   uint32_t last_off = 0, last_cnt = 0;
   if (n > 0) {
@@ -400,15 +355,10 @@ mgx_status mgx_build_bins_range(mgx_context *ctx, const uint32_t *lo, const uint
 
   // Stable 3-bit radix sort: within a bin, rows stay in ascending id order;
   // key 4 (dropped rows) lands past the used prefix.
-  size_t tmp_bytes = 0;
-  auto err = rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys, keys_out, vals,
-                                       (uint32_t *)bins->rows, rows, 0, 3, ctx->stream);
-  if (err != hipSuccess) return MGX_ERR_HIP;
-  void *tmp = nullptr;
-  MGX_TRY(ctx->reserve(tmp_bytes, &tmp));
-  err = rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, keys_out, vals,
-                                  (uint32_t *)bins->rows, rows, 0, 3, ctx->stream);
-  if (err != hipSuccess) return MGX_ERR_HIP;
+  MGX_TRY(mgx_with_temp(ctx, "degree-bin sort", [&](void *tmp, size_t &bytes) {
+    return rocprim::radix_sort_pairs(tmp, bytes, keys, keys_out, vals,
+                                     (uint32_t *)bins->rows, rows, 0, 3, ctx->stream);
+  }));
 
   uint32_t h_counts[5] = {0, 0, 0, 0, 0};
   MGX_HIP_TRY(hipMemcpyAsync(h_counts, counts5, 20, hipMemcpyDeviceToHost, ctx->stream));
@@ -566,18 +516,12 @@ mgx_status mgx_build_from_device_coo(mgx_context *ctx, const int32_t *d_src,
       int32_t *iota = nullptr;
       MGX_HIP_TRY(mgx_hip_malloc(&deg_sorted, (V > 0 ? V : 1) * sizeof(uint32_t)));
       MGX_HIP_TRY(mgx_hip_malloc(&iota, (V > 0 ? V : 1) * sizeof(int32_t)));
-      hipLaunchKernelGGL(k_iota_i32g, dim3(grid_for(V)), dim3(kBlock), 0, ctx->stream, V,
-                         iota);
-      size_t tmp_bytes = 0;
-      auto err = rocprim::radix_sort_pairs_desc(nullptr, tmp_bytes, g->out_degree,
-                                                deg_sorted, iota, g->order, V, 0, 32,
-                                                ctx->stream);
-      if (err != hipSuccess) return MGX_ERR_HIP;
-      void *tmp = nullptr;
-      MGX_TRY(ctx->reserve(tmp_bytes, &tmp));
-      err = rocprim::radix_sort_pairs_desc(tmp, tmp_bytes, g->out_degree, deg_sorted, iota,
-                                           g->order, V, 0, 32, ctx->stream);
-      if (err != hipSuccess) return MGX_ERR_HIP;
+      hipLaunchKernelGGL(mgx_k_iota<int32_t>, dim3(grid_for(V)), dim3(kBlock), 0,
+                         ctx->stream, V, iota);
+      MGX_TRY(mgx_with_temp(ctx, "hot-first degree sort", [&](void *tmp, size_t &bytes) {
+        return rocprim::radix_sort_pairs_desc(tmp, bytes, g->out_degree, deg_sorted, iota,
+                                              g->order, V, 0, 32, ctx->stream);
+      }));
       hipLaunchKernelGGL(k_invert_perm, dim3(grid_for(V)), dim3(kBlock), 0, ctx->stream, V,
                          g->order, d_perm);
       // out_degree / inv_outdeg move to the permuted space.
@@ -739,14 +683,6 @@ mgx_status mgx_upload_coo(mgx_context *ctx, const int64_t *src, const int64_t *d
   return MGX_OK;
 }
 
-namespace {
-__global__ void k_i32_to_i64(int64_t n, const int32_t *in, int64_t *out) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    out[i] = (int64_t)in[i];
-}
-}  // namespace
-
 // Test support: device-generate an edge list and download it (int64), so
 // tests can check bit-identity with the numpy/C generators.
 extern "C" mgx_status mgx_gen_edges_to_host(mgx_context *ctx, int rmat, int scale,
@@ -766,13 +702,13 @@ extern "C" mgx_status mgx_gen_edges_to_host(mgx_context *ctx, int rmat, int scal
     s = mgx_gen_uniform_device(ctx, n_vertices, n_edges, seed, d_src, d_dst);
   }
   if (s == MGX_OK) {
-    hipLaunchKernelGGL(k_i32_to_i64, dim3(grid_for(n_edges)), dim3(kBlock), 0, ctx->stream,
-                       n_edges, d_src, d_wide);
+    hipLaunchKernelGGL((mgx_k_widen<int32_t, int64_t>), dim3(grid_for(n_edges)), dim3(kBlock),
+                       0, ctx->stream, n_edges,d_src, d_wide);
     (void)hipMemcpyAsync(out_src, d_wide, n_edges * sizeof(int64_t), hipMemcpyDeviceToHost,
                          ctx->stream);
     (void)hipStreamSynchronize(ctx->stream);
-    hipLaunchKernelGGL(k_i32_to_i64, dim3(grid_for(n_edges)), dim3(kBlock), 0, ctx->stream,
-                       n_edges, d_dst, d_wide);
+    hipLaunchKernelGGL((mgx_k_widen<int32_t, int64_t>), dim3(grid_for(n_edges)), dim3(kBlock),
+                       0, ctx->stream, n_edges,d_dst, d_wide);
     (void)hipMemcpyAsync(out_dst, d_wide, n_edges * sizeof(int64_t), hipMemcpyDeviceToHost,
                          ctx->stream);
     (void)hipStreamSynchronize(ctx->stream);

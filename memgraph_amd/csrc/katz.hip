@@ -12,26 +12,14 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "mgx_internal.h"
+#include "mgx_device.h"
 
 namespace {
-
-constexpr int kBlock = 256;
-
-inline int64_t grid_for(int64_t work, int64_t cap = 4096) {
-  int64_t g = (work + kBlock - 1) / kBlock;
-  if (g < 1) g = 1;
-  return g > cap ? cap : g;
-}
 
 struct KatzArgs {
   const uint32_t *row_ptr;
   const int32_t *col;
-  const int32_t *bin_rows;
-  int64_t n[4];
-  int64_t off[4];
-  int64_t goff[4];
-  int64_t grid[4];
+  mgx_bin_sections bins;
   const double *omega_old;
   double *omega_new;
   double *centrality;
@@ -43,73 +31,27 @@ struct KatzArgs {
 
 template <int LANES>
 __device__ inline void katz_rows(const KatzArgs &A, int sec, int64_t block_in_sec) {
-  constexpr int RPB = kBlock / LANES;
-  const int64_t nrows = A.n[sec];
-  const int32_t *rows_list = A.bin_rows + A.off[sec];
-  const int sub = threadIdx.x % LANES;
-  __shared__ double red[4];
-  for (int64_t base = block_in_sec * RPB; base < nrows; base += A.grid[sec] * RPB) {
-    const int64_t ri = base + threadIdx.x / LANES;
-    double acc = 0.0;
-    int32_t row = -1;
-    if (ri < nrows) {
-      row = rows_list[ri];
-      const uint32_t s = A.row_ptr[row], e = A.row_ptr[row + 1];
-      if constexpr (LANES >= 64) {
-        // Same access shape as the PageRank sweep: scalar head to 16-B
-        // alignment, int4 nontemporal col loads, 4 gathers in flight.
-        uint32_t s_al = (s + 3u) & ~3u;
-        if (s_al > e) s_al = e;
-        for (uint32_t j = s + sub; j < s_al; j += LANES) acc += A.omega_old[A.col[j]];
-        const uint32_t nvec = (e - s_al) / 4;
-        typedef int v4i __attribute__((ext_vector_type(4)));
-        const v4i *col4 = reinterpret_cast<const v4i *>(A.col + s_al);
-        for (uint32_t c = sub; c < nvec; c += LANES) {
-          const v4i cc = __builtin_nontemporal_load(col4 + c);
-          acc += A.omega_old[cc.x];
-          acc += A.omega_old[cc.y];
-          acc += A.omega_old[cc.z];
-          acc += A.omega_old[cc.w];
-        }
-        for (uint32_t j = s_al + nvec * 4 + sub; j < e; j += LANES)
-          acc += A.omega_old[A.col[j]];
-      } else {
-        for (uint32_t j = s + sub; j < e; j += LANES)
-          acc += A.omega_old[__builtin_nontemporal_load(A.col + j)];
-      }
-    }
-    if constexpr (LANES <= 64) {
-      for (int o = LANES / 2; o; o >>= 1) acc += __shfl_down(acc, o, LANES);
-    } else {
-      for (int o = 32; o; o >>= 1) acc += __shfl_down(acc, o, 64);
-      if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-      __syncthreads();
-      if (threadIdx.x == 0) acc = red[0] + red[1] + red[2] + red[3];
-    }
-    if (sub == 0 && row >= 0 && (LANES <= 64 || threadIdx.x == 0)) {
-      A.omega_new[row] = acc;
-      const double c = A.centrality[row] + A.a_i * acc;
-      A.centrality[row] = c;
-      A.lr[row] = c;                       // katz.cpp:247
-      A.ur[row] = c + A.a_i1g * acc;       // katz.cpp:248-250
-    }
-    if constexpr (LANES > 64) __syncthreads();
-  }
+  reduce_bin_rows<LANES>(
+      A.bins, sec, block_in_sec, 0.0, mgx_op_add(),
+      [&](int32_t row, int sub) {
+        double acc = 0.0;
+        row_gather<LANES>(A.col, A.row_ptr[row], A.row_ptr[row + 1], sub,
+                          [&](int32_t c) { acc += A.omega_old[c]; });
+        return acc;
+      },
+      [&](int32_t row, double acc) {
+        A.omega_new[row] = acc;
+        const double c = A.centrality[row] + A.a_i * acc;
+        A.centrality[row] = c;
+        A.lr[row] = c;                       // katz.cpp:247
+        A.ur[row] = c + A.a_i1g * acc;       // katz.cpp:248-250
+      });
 }
 
 __global__ void __launch_bounds__(kBlock) k_katz_sweep(KatzArgs A) {
-  const int64_t b = blockIdx.x;
-  int sec = 3;
-  if (b < A.goff[1]) sec = 0;
-  else if (b < A.goff[2]) sec = 1;
-  else if (b < A.goff[3]) sec = 2;
-  const int64_t bis = b - A.goff[sec];
-  switch (sec) {
-    case 0: katz_rows<4>(A, 0, bis); break;
-    case 1: katz_rows<16>(A, 1, bis); break;
-    case 2: katz_rows<64>(A, 2, bis); break;
-    default: katz_rows<256>(A, 3, bis); break;
-  }
+  for_bin_section(A.bins.goff, [&](auto lanes, int sec, int64_t bis) {
+    katz_rows<decltype(lanes)::value>(A, sec, bis);
+  });
 }
 
 __global__ void k_scatter_f64(int64_t n, const double *in, const int32_t *order,
@@ -117,12 +59,6 @@ __global__ void k_scatter_f64(int64_t n, const double *in, const int32_t *order,
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x)
     out[order ? order[i] : i] = in[i];
-}
-
-__global__ void k_fill_f64(int64_t n, double v, double *p) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    p[i] = v;
 }
 
 // Stage the convergence-sort input in ORIGINAL vertex order so the stable
@@ -144,15 +80,7 @@ __global__ void k_max_u32(int64_t n, const uint32_t *x, uint32_t *out) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x)
     m = max(m, x[i]);
-  __shared__ uint32_t red[kBlock / 64];
-  for (int o = 32; o; o >>= 1) m = max(m, __shfl_down(m, o, 64));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t s = red[0];
-    for (int i = 1; i < kBlock / 64; ++i) s = max(s, red[i]);
-    atomicMax(out, s);
-  }
+  block_reduce_atomic(m, 0u, mgx_op_max(), [&](uint32_t s) { atomicMax(out, s); });
 }
 
 // Adjacent-pair convergence test over the descending-sorted order
@@ -200,7 +128,7 @@ mgx_status mgx_katz_impl(mgx_context *ctx, mgx_graph *g, double alpha, double ep
   MGX_TRY(ctx->alloc_async((void **)&cent, V * sizeof(double)));
   MGX_TRY(ctx->alloc_async((void **)&lr, V * sizeof(double)));
   MGX_TRY(ctx->alloc_async((void **)&ur, V * sizeof(double)));
-  hipLaunchKernelGGL(k_fill_f64, dim3((uint32_t)grid_for(V)), dim3(kBlock), 0, ctx->stream,
+  hipLaunchKernelGGL(mgx_k_fill<double>, dim3((uint32_t)grid_for(V)), dim3(kBlock), 0, ctx->stream,
                      V, 1.0, omega[0]);  // omega_0 = 1 (katz.cpp:41-44)
   MGX_HIP_TRY(hipMemsetAsync(cent, 0, V * sizeof(double), ctx->stream));
   MGX_HIP_TRY(hipMemsetAsync(lr, 0, V * sizeof(double), ctx->stream));
@@ -218,16 +146,7 @@ mgx_status mgx_katz_impl(mgx_context *ctx, mgx_graph *g, double alpha, double ep
   KatzArgs A;
   A.row_ptr = g->in_row_ptr;
   A.col = g->in_col;
-  A.bin_rows = g->bins_in.rows;
-  int64_t off = 0, goff = 0;
-  for (int b = 0; b < 4; ++b) {
-    A.n[b] = g->bins_in.count[b];
-    A.off[b] = off;
-    off += A.n[b];
-    A.goff[b] = goff;
-    A.grid[b] = g->bins_in.grid[b];
-    goff += A.grid[b];
-  }
+  const int64_t goff = mgx_fill_sections(g->bins_in, &A.bins);
   A.centrality = cent;
   A.lr = lr;
   A.ur = ur;
@@ -249,16 +168,11 @@ mgx_status mgx_katz_impl(mgx_context *ctx, mgx_graph *g, double alpha, double ep
     // tie rule; values are permuted indices for the lr/ur lookups.
     hipLaunchKernelGGL(k_sort_stage, dim3((uint32_t)grid_for(V)), dim3(kBlock), 0,
                        ctx->stream, V, cent, g->order, keys_in, vals_in);
-    size_t tmp_bytes = 0;
-    auto err = rocprim::radix_sort_pairs_desc(nullptr, tmp_bytes, keys_in, keys_out,
-                                              vals_in, vals_out, V, 0, 64, ctx->stream);
-    if (err != hipSuccess) { status = MGX_ERR_HIP; break; }
-    void *tmp = nullptr;
-    status = ctx->reserve(tmp_bytes, &tmp);
+    status = mgx_with_temp(ctx, "katz convergence sort", [&](void *tmp, size_t &bytes) {
+      return rocprim::radix_sort_pairs_desc(tmp, bytes, keys_in, keys_out, vals_in, vals_out,
+                                            V, 0, 64, ctx->stream);
+    });
     if (status != MGX_OK) break;
-    err = rocprim::radix_sort_pairs_desc(tmp, tmp_bytes, keys_in, keys_out, vals_in,
-                                         vals_out, V, 0, 64, ctx->stream);
-    if (err != hipSuccess) { status = MGX_ERR_HIP; break; }
 
     MGX_HIP_TRY(hipMemsetAsync(d_flag, 0, 4, ctx->stream));
     hipLaunchKernelGGL(k_katz_check, dim3((uint32_t)grid_for(V)), dim3(kBlock), 0,

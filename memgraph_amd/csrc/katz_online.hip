@@ -45,18 +45,11 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "mgx_internal.h"
+#include "mgx_device.h"
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr uint32_t kBigRow = 256;  // >=: block-per-row gather
-
-inline int64_t grid_for(int64_t work, int64_t cap = 4096) {
-  int64_t g = (work + kBlock - 1) / kBlock;
-  if (g < 1) g = 1;
-  return g > cap ? cap : g;
-}
 
 struct KOnState {
   std::unordered_map<int64_t, int32_t> mg2slot;
@@ -77,12 +70,6 @@ struct KOnState {
 KOnState g_k;
 
 // ---- kernels -------------------------------------------------------------
-
-__global__ void k_fill_f64(int64_t n, double v, double *p) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    p[i] = v;
-}
 
 // Fused gather + centrality/bounds update for one iteration over SMALL rows
 // (KatzCentralityLoop body :218-235). Arrays indexed by SLOT; the graph is
@@ -319,7 +306,7 @@ mgx_status kon_grow_slots(mgx_context *ctx, int64_t need) {
   auto grow = [&](double **p, double init) -> mgx_status {
     double *np = nullptr;
     MGX_HIP_TRY(mgx_hip_malloc(&np, cap * 8));
-    hipLaunchKernelGGL(k_fill_f64, dim3((uint32_t)grid_for(cap)), dim3(kBlock), 0,
+    hipLaunchKernelGGL(mgx_k_fill<double>, dim3((uint32_t)grid_for(cap)), dim3(kBlock), 0,
                        ctx->stream, cap, init, np);
     if (*p && g_k.slots_cap > 0) {
       MGX_HIP_TRY(hipMemcpyAsync(np, *p, g_k.slots_cap * 8, hipMemcpyDeviceToDevice,
@@ -357,10 +344,10 @@ mgx_status kon_add_iteration(mgx_context *ctx, double omega_init) {
   double *w = nullptr, *c = nullptr;
   MGX_HIP_TRY(mgx_hip_malloc(&w, g_k.slots_cap * 8));
   MGX_HIP_TRY(mgx_hip_malloc(&c, g_k.slots_cap * 8));
-  hipLaunchKernelGGL(k_fill_f64, dim3((uint32_t)grid_for(g_k.slots_cap)), dim3(kBlock), 0,
-                     ctx->stream, g_k.slots_cap, omega_init, w);
-  hipLaunchKernelGGL(k_fill_f64, dim3((uint32_t)grid_for(g_k.slots_cap)), dim3(kBlock), 0,
-                     ctx->stream, g_k.slots_cap, 0.0, c);
+  hipLaunchKernelGGL(mgx_k_fill<double>, dim3((uint32_t)grid_for(g_k.slots_cap)),
+                     dim3(kBlock), 0, ctx->stream, g_k.slots_cap, omega_init, w);
+  hipLaunchKernelGGL(mgx_k_fill<double>, dim3((uint32_t)grid_for(g_k.slots_cap)),
+                     dim3(kBlock), 0, ctx->stream, g_k.slots_cap, 0.0, c);
   g_k.omega.push_back(w);
   g_k.cent.push_back(c);
   return MGX_OK;
@@ -486,15 +473,11 @@ mgx_status kon_loop(mgx_context *ctx, mgx_graph *g, const KMaps &m, double gamma
     if (n_active <= 1) break;
     hipLaunchKernelGGL(k_conv_keys, dim3((uint32_t)grid_for(n_active)), dim3(kBlock), 0,
                        ctx->stream, n_active, d_act, g_k.cent[i], d_keys);
-    size_t tmp_bytes = 0;
-    auto err = rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_keys, d_keys_sorted, d_act,
-                                         d_act_sorted, n_active, 0, 64, ctx->stream);
-    if (err != hipSuccess) { st = MGX_ERR_HIP; break; }
-    void *tmp = nullptr;
-    MGX_TRY(ctx->reserve(tmp_bytes, &tmp));
-    err = rocprim::radix_sort_pairs(tmp, tmp_bytes, d_keys, d_keys_sorted, d_act,
-                                    d_act_sorted, n_active, 0, 64, ctx->stream);
-    if (err != hipSuccess) { st = MGX_ERR_HIP; break; }
+    st = mgx_with_temp(ctx, "katz_online convergence sort", [&](void *tmp, size_t &bytes) {
+      return rocprim::radix_sort_pairs(tmp, bytes, d_keys, d_keys_sorted, d_act, d_act_sorted,
+                                       n_active, 0, 64, ctx->stream);
+    });
+    if (st != MGX_OK) break;
     MGX_HIP_TRY(hipMemsetAsync(d_flag, 0, 4, ctx->stream));
     hipLaunchKernelGGL(k_conv_check, dim3((uint32_t)grid_for(n_active)), dim3(kBlock), 0,
                        ctx->stream, n_active, d_act_sorted, g_k.lr, g_k.ur, g_k.eps,
@@ -750,8 +733,8 @@ extern "C" mgx_status mgx_konline_update(mgx_context *ctx, mgx_graph *g,
       return MGX_ERR_OUT_OF_MEMORY;
     }
   }
-  hipLaunchKernelGGL(k_fill_f64, dim3((uint32_t)grid_for(g_k.slots_cap)), dim3(kBlock), 0,
-                     ctx->stream, g_k.slots_cap, 1.0, new_omega[0]);
+  hipLaunchKernelGGL(mgx_k_fill<double>, dim3((uint32_t)grid_for(g_k.slots_cap)),
+                     dim3(kBlock), 0, ctx->stream, g_k.slots_cap, 1.0, new_omega[0]);
 
   // updated/frontier state in dense space
   uint32_t *d_updated = nullptr;

@@ -44,17 +44,9 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "mgx_internal.h"
+#include "mgx_device.h"
 
 namespace {
-
-constexpr int kBlock = 256;
-
-inline int64_t grid_for(int64_t work, int64_t cap = 4096) {
-  int64_t g = (work + kBlock - 1) / kBlock;
-  if (g < 1) g = 1;
-  return g > cap ? cap : g;
-}
 
 struct LrtState {
   std::unordered_map<int64_t, int32_t> mg2slot;

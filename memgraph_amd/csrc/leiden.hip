@@ -47,7 +47,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "../../include/mgx_graphgen.h"
-#include "mgx_internal.h"
+#include "mgx_device.h"
 
 namespace {
 
@@ -68,15 +68,8 @@ inline bool leiden_trace() {
     }                                      \
   } while (0)
 
-constexpr int kBlock = 256;
 constexpr uint32_t kSmallRowDeg = 256;
 constexpr int kLdsCap = 512;
-
-inline int64_t grid_for(int64_t work, int64_t cap = 4096) {
-  int64_t g = (work + kBlock - 1) / kBlock;
-  if (g < 1) g = 1;
-  return g > cap ? cap : g;
-}
 
 struct Level {
   int64_t nv = 0;
@@ -93,26 +86,6 @@ void free_level(Level *L) {
   if (L->w) (void)hipFree(L->w);
   if (L->node_w) (void)hipFree(L->node_w);
   *L = Level{};
-}
-
-// ---- generic kernels ----------------------------------------------------
-
-__global__ void k_iota32(int64_t n, int32_t *p) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    p[i] = (int32_t)i;
-}
-
-__global__ void k_fill32(int64_t n, int32_t v, int32_t *p) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    p[i] = v;
-}
-
-__global__ void k_fillu32(int64_t n, uint32_t v, uint32_t *p) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    p[i] = v;
 }
 
 // ---- MoveNodesFast as red-black CPM sweeps ------------------------------
@@ -570,10 +543,10 @@ extern "C" mgx_status mgx_leiden(mgx_context *ctx, mgx_graph *g, double gamma,
   uint32_t *d_csize = nullptr;
   MGX_HIP_TRY(mgx_hip_malloc(&d_comm, V * 4));
   MGX_HIP_TRY(mgx_hip_malloc(&d_csize, V * 4));
-  hipLaunchKernelGGL(k_iota32, dim3((uint32_t)grid_for(V)), dim3(kBlock), 0, ctx->stream,
-                     V, d_comm);
-  hipLaunchKernelGGL(k_fillu32, dim3((uint32_t)grid_for(V)), dim3(kBlock), 0, ctx->stream,
-                     V, 1u, d_csize);
+  hipLaunchKernelGGL(mgx_k_iota<int32_t>, dim3((uint32_t)grid_for(V)), dim3(kBlock), 0,
+                     ctx->stream, V, d_comm);
+  hipLaunchKernelGGL(mgx_k_fill<uint32_t>, dim3((uint32_t)grid_for(V)), dim3(kBlock), 0,
+                     ctx->stream, V, 1u, d_csize);
 
   while (!done && st == MGX_OK) {
     ++iters;
@@ -670,9 +643,9 @@ extern "C" mgx_status mgx_leiden(mgx_context *ctx, mgx_graph *g, double gamma,
                              dim3(kBlock), 0, ctx->stream, M);
         if (!brows.empty()) {
           if (pool_total > 0) {
-            hipLaunchKernelGGL(k_fill32, dim3((uint32_t)grid_for((int64_t)pool_total)),
-                               dim3(kBlock), 0, ctx->stream, (int64_t)pool_total, -1,
-                               d_pkeys);
+            hipLaunchKernelGGL(mgx_k_fill<int32_t>,
+                               dim3((uint32_t)grid_for((int64_t)pool_total)), dim3(kBlock),
+                               0, ctx->stream, (int64_t)pool_total, -1, d_pkeys);
             MGX_HIP_TRY(hipMemsetAsync(d_pvals, 0, pool_total * 8, ctx->stream));
           }
           hipLaunchKernelGGL(
@@ -764,7 +737,7 @@ extern "C" mgx_status mgx_leiden(mgx_context *ctx, mgx_graph *g, double gamma,
       MGX_HIP_TRY(hipMemcpyAsync(d_memoff, mem_off.data(), (nv + 1) * 4,
                                  hipMemcpyHostToDevice, ctx->stream));
       // rcomm starts singleton-local: filled per subset inside k_refine
-      hipLaunchKernelGGL(k_fill32, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0,
+      hipLaunchKernelGGL(mgx_k_fill<int32_t>, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0,
                          ctx->stream, nv, 0, d_rcomm);
       MGX_HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, ctx->stream));
       RefineArgs R;

@@ -35,11 +35,10 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "mgx_internal.h"
+#include "mgx_device.h"
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr uint32_t kSmallRowDeg = 256;  // <: wave+LDS table; >=: block+pool
 constexpr int kLdsCap = 512;            // per-wave table entries (>= 2*255)
 
@@ -93,12 +92,6 @@ inline bool louvain_debug() {
       fflush(stderr);                                                         \
     }                                                                         \
   } while (0)
-
-inline int64_t grid_for(int64_t work, int64_t cap = 4096) {
-  int64_t g = (work + kBlock - 1) / kBlock;
-  if (g < 1) g = 1;
-  return g > cap ? cap : g;
-}
 
 struct Level {
   int64_t nv = 0;
@@ -170,15 +163,7 @@ __global__ void k_sum_f64(int64_t n, const double *x, double *out) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x)
     acc += x[i];
-  __shared__ double red[kBlock / 64];
-  for (int o = 32; o; o >>= 1) acc += __shfl_down(acc, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0.0;
-    for (int i = 0; i < kBlock / 64; ++i) s += red[i];
-    atomicAdd(out, s);
-  }
+  block_reduce_atomic(acc, 0.0, mgx_op_add(), [&](double s) { atomicAdd(out, s); });
 }
 
 __global__ void k_sum_sq_f64(int64_t n, const double *x, double *out) {
@@ -186,27 +171,7 @@ __global__ void k_sum_sq_f64(int64_t n, const double *x, double *out) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x)
     acc += x[i] * x[i];
-  __shared__ double red[kBlock / 64];
-  for (int o = 32; o; o >>= 1) acc += __shfl_down(acc, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0.0;
-    for (int i = 0; i < kBlock / 64; ++i) s += red[i];
-    atomicAdd(out, s);
-  }
-}
-
-__global__ void k_iota_i32(int64_t n, int32_t *p) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    p[i] = (int32_t)i;
-}
-
-__global__ void k_fill_i32(int64_t n, int32_t v, int32_t *p) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    p[i] = v;
+  block_reduce_atomic(acc, 0.0, mgx_op_add(), [&](double s) { atomicAdd(out, s); });
 }
 
 __global__ void k_apply_updates(int64_t nv, double *cinfo_deg, int32_t *cinfo_size,
@@ -770,10 +735,10 @@ mgx_status louvain_level(mgx_context *ctx, const Level &L, double lower, double 
   MGX_HIP_TRY(scalars.alloc(ctx, 3 * 8));  // [e_xx, a2_x, total_w]
 
   MGX_HIP_TRY(hipMemsetAsync(scalars.as<double>() + 2, 0, 8, ctx->stream));
-  hipLaunchKernelGGL(k_iota_i32, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0, ctx->stream,
-                     nv, past.as<int32_t>());
-  hipLaunchKernelGGL(k_iota_i32, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0, ctx->stream,
-                     nv, curr.as<int32_t>());
+  hipLaunchKernelGGL(mgx_k_iota<int32_t>, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0,
+                     ctx->stream, nv, past.as<int32_t>());
+  hipLaunchKernelGGL(mgx_k_iota<int32_t>, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0,
+                     ctx->stream, nv, curr.as<int32_t>());
   MGX_HIP_TRY(hipMemsetAsync(cupd_deg.p, 0, nv * 8, ctx->stream));
   MGX_HIP_TRY(hipMemsetAsync(cupd_size.p, 0, nv * 4, ctx->stream));
 
@@ -843,17 +808,11 @@ mgx_status louvain_level(mgx_context *ctx, const Level &L, double lower, double 
                        ctx->stream, n_big, big_rows.as<int32_t>(), L.row_ptr,
                        caps.as<uint64_t>());
     MGX_HIP_TRY(pool_off.alloc(ctx, (n_big + 1) * 8));
-    size_t tmp_bytes = 0;
-    auto err = rocprim::exclusive_scan(nullptr, tmp_bytes, caps.as<uint64_t>(),
-                                       pool_off.as<uint64_t>(), (uint64_t)0, n_big,
-                                       rocprim::plus<uint64_t>(), ctx->stream);
-    if (err != hipSuccess) return MGX_ERR_HIP;
-    void *tmp = nullptr;
-    MGX_TRY(ctx->reserve(tmp_bytes, &tmp));
-    err = rocprim::exclusive_scan(tmp, tmp_bytes, caps.as<uint64_t>(),
-                                  pool_off.as<uint64_t>(), (uint64_t)0, n_big,
-                                  rocprim::plus<uint64_t>(), ctx->stream);
-    if (err != hipSuccess) return MGX_ERR_HIP;
+    MGX_TRY(mgx_with_temp(ctx, "louvain pool scan", [&](void *tmp, size_t &bytes) {
+      return rocprim::exclusive_scan(tmp, bytes, caps.as<uint64_t>(), pool_off.as<uint64_t>(),
+                                     (uint64_t)0, n_big, rocprim::plus<uint64_t>(),
+                                     ctx->stream);
+    }));
     uint64_t last_off = 0, last_cap = 0;
     MGX_HIP_TRY(hipMemcpyAsync(&last_off, pool_off.as<uint64_t>() + n_big - 1, 8,
                                hipMemcpyDeviceToHost, ctx->stream));
@@ -945,9 +904,9 @@ mgx_status louvain_level(mgx_context *ctx, const Level &L, double lower, double 
     if (n_big > 0) {
       if (!A.inkernel_clear) {
         MGX_LTRACE("it=%lld pool_clear", (long long)iters);
-        hipLaunchKernelGGL(k_fill_i32, dim3((uint32_t)grid_for((int64_t)pool_total)),
-                           dim3(kBlock), 0, ctx->stream, (int64_t)pool_total, -1,
-                           pool_keys.as<int32_t>());
+        hipLaunchKernelGGL(mgx_k_fill<int32_t>,
+                           dim3((uint32_t)grid_for((int64_t)pool_total)), dim3(kBlock), 0,
+                           ctx->stream, (int64_t)pool_total, -1, pool_keys.as<int32_t>());
         MGX_HIP_TRY(hipMemsetAsync(pool_vals.p, 0, pool_total * 8, ctx->stream));
       }
       const int64_t blocks = n_big < 4096 ? n_big : 4096;
@@ -1041,27 +1000,21 @@ mgx_status louvain_level(mgx_context *ctx, const Level &L, double lower, double 
 mgx_status renumber(mgx_context *ctx, int32_t *C, int64_t nv, int64_t *n_clusters) {
   DevBuf rep, keys_out, cand, cand_out, newid, nact;
   MGX_HIP_TRY(rep.alloc(ctx, nv * 4));
-  hipLaunchKernelGGL(k_fill_i32, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0, ctx->stream,
-                     nv, INT32_MAX, rep.as<int32_t>());
+  hipLaunchKernelGGL(mgx_k_fill<int32_t>, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0,
+                     ctx->stream, nv, INT32_MAX, rep.as<int32_t>());
   hipLaunchKernelGGL(k_rep_min, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0, ctx->stream,
                      nv, C, rep.as<int32_t>());
   // sort (rep, c) ascending by rep; INT32_MAX reps (inactive ids) sort last.
   MGX_HIP_TRY(cand.alloc(ctx, nv * 4));
   MGX_HIP_TRY(cand_out.alloc(ctx, nv * 4));
   MGX_HIP_TRY(keys_out.alloc(ctx, nv * 4));
-  hipLaunchKernelGGL(k_iota_i32, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0, ctx->stream,
-                     nv, cand.as<int32_t>());
-  size_t tmp_bytes = 0;
-  auto err = rocprim::radix_sort_pairs(nullptr, tmp_bytes, (uint32_t *)rep.p,
-                                       (uint32_t *)keys_out.p, cand.as<int32_t>(),
-                                       cand_out.as<int32_t>(), nv, 0, 32, ctx->stream);
-  if (err != hipSuccess) return MGX_ERR_HIP;
-  void *tmp = nullptr;
-  MGX_TRY(ctx->reserve(tmp_bytes, &tmp));
-  err = rocprim::radix_sort_pairs(tmp, tmp_bytes, (uint32_t *)rep.p,
-                                  (uint32_t *)keys_out.p, cand.as<int32_t>(),
-                                  cand_out.as<int32_t>(), nv, 0, 32, ctx->stream);
-  if (err != hipSuccess) return MGX_ERR_HIP;
+  hipLaunchKernelGGL(mgx_k_iota<int32_t>, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0,
+                     ctx->stream, nv, cand.as<int32_t>());
+  MGX_TRY(mgx_with_temp(ctx, "louvain renumber sort", [&](void *tmp, size_t &bytes) {
+    return rocprim::radix_sort_pairs(tmp, bytes, (uint32_t *)rep.p, (uint32_t *)keys_out.p,
+                                     cand.as<int32_t>(), cand_out.as<int32_t>(), nv, 0, 32,
+                                     ctx->stream);
+  }));
   // count active = reps != INT32_MAX: binary property; count via reduce on
   // host copy of the boundary — simpler: count nonzero with a kernel.
   DevBuf count;
@@ -1164,33 +1117,21 @@ mgx_status coarsen(mgx_context *ctx, const Level &in, const int32_t *C, int64_t 
     MGX_LTRACE("coarsen PAIRKEYS bad=%llu", bad);
     MGX_HIP_TRY(hipMemsetAsync(d_bad.p, 0, 8, ctx->stream));
   }
-  size_t tmp_bytes = 0;
-  auto err = rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys.as<uint64_t>(),
-                                       keys_sorted.as<uint64_t>(), vals.as<double>(),
-                                       vals_sorted.as<double>(), ne2, 0, 64, ctx->stream);
-  if (err != hipSuccess) return MGX_ERR_HIP;
-  void *tmp = nullptr;
-  MGX_TRY(ctx->reserve(tmp_bytes, &tmp));
-  err = rocprim::radix_sort_pairs(tmp, tmp_bytes, keys.as<uint64_t>(),
-                                  keys_sorted.as<uint64_t>(), vals.as<double>(),
-                                  vals_sorted.as<double>(), ne2, 0, 64, ctx->stream);
-  if (err != hipSuccess) return MGX_ERR_HIP;
+  MGX_TRY(mgx_with_temp(ctx, "louvain coarsen pair sort", [&](void *tmp, size_t &bytes) {
+    return rocprim::radix_sort_pairs(tmp, bytes, keys.as<uint64_t>(),
+                                     keys_sorted.as<uint64_t>(), vals.as<double>(),
+                                     vals_sorted.as<double>(), ne2, 0, 64, ctx->stream);
+  }));
   MGX_HIP_TRY(u_keys.alloc(ctx, ne2 * 8));
   MGX_HIP_TRY(u_vals.alloc(ctx, ne2 * 8));
   MGX_HIP_TRY(u_count.alloc(ctx, 8));
-  err = rocprim::reduce_by_key(nullptr, tmp_bytes, keys_sorted.as<uint64_t>(),
-                               vals_sorted.as<double>(), ne2, u_keys.as<uint64_t>(),
-                               u_vals.as<double>(), (unsigned int *)u_count.p,
-                               rocprim::plus<double>(), rocprim::equal_to<uint64_t>(),
-                               ctx->stream);
-  if (err != hipSuccess) return MGX_ERR_HIP;
-  MGX_TRY(ctx->reserve(tmp_bytes, &tmp));
-  err = rocprim::reduce_by_key(tmp, tmp_bytes, keys_sorted.as<uint64_t>(),
-                               vals_sorted.as<double>(), ne2, u_keys.as<uint64_t>(),
-                               u_vals.as<double>(), (unsigned int *)u_count.p,
-                               rocprim::plus<double>(), rocprim::equal_to<uint64_t>(),
-                               ctx->stream);
-  if (err != hipSuccess) return MGX_ERR_HIP;
+  MGX_TRY(mgx_with_temp(ctx, "louvain coarsen reduce_by_key", [&](void *tmp, size_t &bytes) {
+    return rocprim::reduce_by_key(tmp, bytes, keys_sorted.as<uint64_t>(),
+                                  vals_sorted.as<double>(), ne2, u_keys.as<uint64_t>(),
+                                  u_vals.as<double>(), (unsigned int *)u_count.p,
+                                  rocprim::plus<double>(), rocprim::equal_to<uint64_t>(),
+                                  ctx->stream);
+  }));
   unsigned int n_unique = 0;
   MGX_HIP_TRY(hipMemcpyAsync(&n_unique, u_count.p, 4, hipMemcpyDeviceToHost, ctx->stream));
   MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1289,13 +1230,10 @@ mgx_status coarsen(mgx_context *ctx, const Level &in, const int32_t *C, int64_t 
     if (cn0 < ws1 && ws0 < cn1) MGX_LTRACE("coarsen ALIAS counts overlaps workspace");
   }
   // exclusive scan counts -> row_ptr
-  err = rocprim::exclusive_scan(nullptr, tmp_bytes, counts.as<uint32_t>(), out->row_ptr,
-                                0u, n_clusters, rocprim::plus<uint32_t>(), ctx->stream);
-  if (err != hipSuccess) return MGX_ERR_HIP;
-  MGX_TRY(ctx->reserve(tmp_bytes, &tmp));
-  err = rocprim::exclusive_scan(tmp, tmp_bytes, counts.as<uint32_t>(), out->row_ptr, 0u,
-                                n_clusters, rocprim::plus<uint32_t>(), ctx->stream);
-  if (err != hipSuccess) return MGX_ERR_HIP;
+  MGX_TRY(mgx_with_temp(ctx, "louvain coarsen row_ptr scan", [&](void *tmp, size_t &bytes) {
+    return rocprim::exclusive_scan(tmp, bytes, counts.as<uint32_t>(), out->row_ptr, 0u,
+                                   n_clusters, rocprim::plus<uint32_t>(), ctx->stream);
+  }));
   uint32_t last_off = 0, last_cnt = 0;
   MGX_HIP_TRY(hipMemcpyAsync(&last_off, out->row_ptr + n_clusters - 1, 4,
                              hipMemcpyDeviceToHost, ctx->stream));
@@ -1464,12 +1402,6 @@ __global__ void k_compose(int64_t nv, int32_t *c_orig, const int32_t *C) {
   }
 }
 
-__global__ void k_widen_i32_to_i64(int64_t n, const int32_t *in, int64_t *out) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    out[i] = (int64_t)in[i];
-}
-
 }  // namespace
 
 mgx_status mgx_louvain_impl(mgx_context *ctx, mgx_graph *g, double threshold,
@@ -1534,7 +1466,7 @@ mgx_status mgx_louvain_impl(mgx_context *ctx, mgx_graph *g, double threshold,
 
   DevBuf c_orig_d, c_level;
   MGX_HIP_TRY(c_orig_d.alloc(ctx, nv0 * 4));
-  hipLaunchKernelGGL(k_fill_i32, dim3((uint32_t)grid_for(nv0)), dim3(kBlock), 0,
+  hipLaunchKernelGGL(mgx_k_fill<int32_t>, dim3((uint32_t)grid_for(nv0)), dim3(kBlock), 0,
                      ctx->stream, nv0, -1, c_orig_d.as<int32_t>());
 
   double prev_mod = -1.0, curr_mod = -1.0;
@@ -1584,8 +1516,8 @@ mgx_status mgx_louvain_impl(mgx_context *ctx, mgx_graph *g, double threshold,
   // Download.
   DevBuf wide;
   MGX_HIP_TRY(wide.alloc(ctx, nv0 * 8));
-  hipLaunchKernelGGL(k_widen_i32_to_i64, dim3((uint32_t)grid_for(nv0)), dim3(kBlock), 0,
-                     ctx->stream, nv0, c_orig_d.as<int32_t>(), wide.as<int64_t>());
+  hipLaunchKernelGGL((mgx_k_widen<int32_t, int64_t>), dim3((uint32_t)grid_for(nv0)),
+                     dim3(kBlock), 0, ctx->stream, nv0, c_orig_d.as<int32_t>(), wide.as<int64_t>());
   if (out_community) {
     MGX_HIP_TRY(hipMemcpyAsync(out_community, wide.p, nv0 * 8, hipMemcpyDeviceToHost,
                                ctx->stream));

@@ -14,20 +14,14 @@
 
 #include <chrono>
 
-#include "mgx_internal.h"
+#include "mgx_device.h"
 
 namespace {
-
-constexpr int kBlock = 256;
 
 struct PrArgs {
   const uint32_t *row_ptr;
   const int32_t *col;
-  const int32_t *bin_rows;
-  int64_t n[4];     // rows per bin
-  int64_t off[4];   // offsets into bin_rows
-  int64_t goff[4];  // grid offsets per section
-  int64_t grid[4];
+  mgx_bin_sections bins;
   const float *contrib_old;
   const float *rank_old;
   float *rank_new;
@@ -48,148 +42,119 @@ struct PrArgs {
   int deep;  // experiment: 4x-unrolled wide path (16 gathers/lane in flight)
 };
 
+// This lane's share of sum_{u->row} contrib[u] over the row's stripe range.
+template <int LANES>
+__device__ inline double pr_row_sum(const PrArgs &A, int32_t row, int sub) {
+  double acc = 0.0;
+  const uint32_t s = A.sp_lo[row], e = A.sp_hi[row];
+  if constexpr (LANES >= 64) {
+    // Wide rows: scalar head to 16-B alignment, then int4 nontemporal
+    // column loads (the col stream is read exactly once — keep it out
+    // of L1 so the contrib gathers stay cached; G13/nt-weights) with 4
+    // independent gathers per lane per iteration for latency hiding.
+    uint32_t s_al = (s + 3u) & ~3u;
+    if (s_al > e) s_al = e;
+    for (uint32_t j = s + sub; j < s_al; j += LANES)
+      acc += (double)A.contrib_old[A.col[j]];
+    const uint32_t nvec = (e - s_al) / 4;
+    typedef int v4i __attribute__((ext_vector_type(4)));
+    const v4i *col4 = reinterpret_cast<const v4i *>(A.col + s_al);
+    uint32_t c = sub;
+    if (A.deep) {
+      // 4x unrolled: 16 independent gathers in flight per lane
+      // (MGX_PR_DEEP_UNROLL experiment).
+      for (; c + 3 * LANES < nvec; c += 4 * LANES) {
+        const v4i c0 = __builtin_nontemporal_load(col4 + c);
+        const v4i c1 = __builtin_nontemporal_load(col4 + c + LANES);
+        const v4i c2 = __builtin_nontemporal_load(col4 + c + 2 * LANES);
+        const v4i c3 = __builtin_nontemporal_load(col4 + c + 3 * LANES);
+        float g[16];
+        g[0] = A.contrib_old[c0.x]; g[1] = A.contrib_old[c0.y];
+        g[2] = A.contrib_old[c0.z]; g[3] = A.contrib_old[c0.w];
+        g[4] = A.contrib_old[c1.x]; g[5] = A.contrib_old[c1.y];
+        g[6] = A.contrib_old[c1.z]; g[7] = A.contrib_old[c1.w];
+        g[8] = A.contrib_old[c2.x]; g[9] = A.contrib_old[c2.y];
+        g[10] = A.contrib_old[c2.z]; g[11] = A.contrib_old[c2.w];
+        g[12] = A.contrib_old[c3.x]; g[13] = A.contrib_old[c3.y];
+        g[14] = A.contrib_old[c3.z]; g[15] = A.contrib_old[c3.w];
+        for (int k = 0; k < 16; ++k) acc += (double)g[k];
+      }
+    }
+    // 2x unrolled: 8 independent gathers in flight per lane.
+    for (; c + LANES < nvec; c += 2 * LANES) {
+      const v4i c0 = __builtin_nontemporal_load(col4 + c);
+      const v4i c1 = __builtin_nontemporal_load(col4 + c + LANES);
+      const float g0 = A.contrib_old[c0.x];
+      const float g1 = A.contrib_old[c0.y];
+      const float g2 = A.contrib_old[c0.z];
+      const float g3 = A.contrib_old[c0.w];
+      const float g4 = A.contrib_old[c1.x];
+      const float g5 = A.contrib_old[c1.y];
+      const float g6 = A.contrib_old[c1.z];
+      const float g7 = A.contrib_old[c1.w];
+      acc += (double)g0;
+      acc += (double)g1;
+      acc += (double)g2;
+      acc += (double)g3;
+      acc += (double)g4;
+      acc += (double)g5;
+      acc += (double)g6;
+      acc += (double)g7;
+    }
+    for (; c < nvec; c += LANES) {
+      const v4i cc = __builtin_nontemporal_load(col4 + c);
+      acc += (double)A.contrib_old[cc.x];
+      acc += (double)A.contrib_old[cc.y];
+      acc += (double)A.contrib_old[cc.z];
+      acc += (double)A.contrib_old[cc.w];
+    }
+    for (uint32_t j = s_al + nvec * 4 + sub; j < e; j += LANES)
+      acc += (double)A.contrib_old[A.col[j]];
+  } else {
+    // Short rows: a LANES-wide group reads consecutive cols (16/64-B
+    // granules); nt keeps the one-pass col stream out of L1.
+    row_gather<LANES>(A.col, s, e, sub,
+                      [&](int32_t c) { acc += (double)A.contrib_old[c]; });
+  }
+  return acc;
+}
+
 template <int LANES>
 __device__ inline float pr_rows(const PrArgs &A, int sec, int64_t block_in_sec) {
-  constexpr int RPB = kBlock / LANES;
-  const int64_t nrows = A.n[sec];
-  const int32_t *rows_list = A.bin_rows + A.off[sec];
-  const int sub = threadIdx.x % LANES;
   float maxd = 0.0f;
-  __shared__ double red[4];
-  for (int64_t base = block_in_sec * RPB; base < nrows; base += A.grid[sec] * RPB) {
-    const int64_t ri = base + threadIdx.x / LANES;
-    double acc = 0.0;
-    int32_t row = -1;
-    if (ri < nrows) {
-      row = rows_list[ri];
-      const uint32_t s = A.sp_lo[row], e = A.sp_hi[row];
-      if constexpr (LANES >= 64) {
-        // Wide rows: scalar head to 16-B alignment, then int4 nontemporal
-        // column loads (the col stream is read exactly once — keep it out
-        // of L1 so the contrib gathers stay cached; G13/nt-weights) with 4
-        // independent gathers per lane per iteration for latency hiding.
-        uint32_t s_al = (s + 3u) & ~3u;
-        if (s_al > e) s_al = e;
-        for (uint32_t j = s + sub; j < s_al; j += LANES)
-          acc += (double)A.contrib_old[A.col[j]];
-        const uint32_t nvec = (e - s_al) / 4;
-        typedef int v4i __attribute__((ext_vector_type(4)));
-        const v4i *col4 = reinterpret_cast<const v4i *>(A.col + s_al);
-        uint32_t c = sub;
-        if (A.deep) {
-          // 4x unrolled: 16 independent gathers in flight per lane
-          // (MGX_PR_DEEP_UNROLL experiment).
-          for (; c + 3 * LANES < nvec; c += 4 * LANES) {
-            const v4i c0 = __builtin_nontemporal_load(col4 + c);
-            const v4i c1 = __builtin_nontemporal_load(col4 + c + LANES);
-            const v4i c2 = __builtin_nontemporal_load(col4 + c + 2 * LANES);
-            const v4i c3 = __builtin_nontemporal_load(col4 + c + 3 * LANES);
-            float g[16];
-            g[0] = A.contrib_old[c0.x]; g[1] = A.contrib_old[c0.y];
-            g[2] = A.contrib_old[c0.z]; g[3] = A.contrib_old[c0.w];
-            g[4] = A.contrib_old[c1.x]; g[5] = A.contrib_old[c1.y];
-            g[6] = A.contrib_old[c1.z]; g[7] = A.contrib_old[c1.w];
-            g[8] = A.contrib_old[c2.x]; g[9] = A.contrib_old[c2.y];
-            g[10] = A.contrib_old[c2.z]; g[11] = A.contrib_old[c2.w];
-            g[12] = A.contrib_old[c3.x]; g[13] = A.contrib_old[c3.y];
-            g[14] = A.contrib_old[c3.z]; g[15] = A.contrib_old[c3.w];
-            for (int k = 0; k < 16; ++k) acc += (double)g[k];
+  reduce_bin_rows<LANES>(
+      A.bins, sec, block_in_sec, 0.0, mgx_op_add(),
+      [&](int32_t row, int sub) { return pr_row_sum<LANES>(A, row, sub); },
+      [&](int32_t row, double acc) {
+        if (A.mode == 1) {
+          A.partial[row] = acc;
+        } else if (A.mode == 2) {
+          A.partial[row] += acc;
+        } else {
+          if (A.mode == 3) acc += A.partial[row];
+          const float newr = (float)((double)A.base_term + (double)A.damping * acc);
+          const int64_t gv = A.row_base + row;
+          A.rank_new[gv] = newr;
+          A.contrib_new[gv] = newr * A.inv_outdeg[gv];
+          if (A.delta_max) {  // old-rank read only paid when Linf is tracked
+            const float d = fabsf(newr - A.rank_old[gv]);
+            if (d > maxd) maxd = d;
           }
         }
-        // 2x unrolled: 8 independent gathers in flight per lane.
-        for (; c + LANES < nvec; c += 2 * LANES) {
-          const v4i c0 = __builtin_nontemporal_load(col4 + c);
-          const v4i c1 = __builtin_nontemporal_load(col4 + c + LANES);
-          const float g0 = A.contrib_old[c0.x];
-          const float g1 = A.contrib_old[c0.y];
-          const float g2 = A.contrib_old[c0.z];
-          const float g3 = A.contrib_old[c0.w];
-          const float g4 = A.contrib_old[c1.x];
-          const float g5 = A.contrib_old[c1.y];
-          const float g6 = A.contrib_old[c1.z];
-          const float g7 = A.contrib_old[c1.w];
-          acc += (double)g0;
-          acc += (double)g1;
-          acc += (double)g2;
-          acc += (double)g3;
-          acc += (double)g4;
-          acc += (double)g5;
-          acc += (double)g6;
-          acc += (double)g7;
-        }
-        for (; c < nvec; c += LANES) {
-          const v4i cc = __builtin_nontemporal_load(col4 + c);
-          acc += (double)A.contrib_old[cc.x];
-          acc += (double)A.contrib_old[cc.y];
-          acc += (double)A.contrib_old[cc.z];
-          acc += (double)A.contrib_old[cc.w];
-        }
-        for (uint32_t j = s_al + nvec * 4 + sub; j < e; j += LANES)
-          acc += (double)A.contrib_old[A.col[j]];
-      } else {
-        // Short rows: a LANES-wide group reads consecutive cols (16/64-B
-        // granules); nt keeps the one-pass col stream out of L1.
-        for (uint32_t j = s + sub; j < e; j += LANES)
-          acc += (double)A.contrib_old[__builtin_nontemporal_load(A.col + j)];
-      }
-    }
-    if constexpr (LANES <= 64) {
-      for (int o = LANES / 2; o; o >>= 1) acc += __shfl_down(acc, o, LANES);
-    } else {
-      for (int o = 32; o; o >>= 1) acc += __shfl_down(acc, o, 64);
-      if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-      __syncthreads();
-      if (threadIdx.x == 0) acc = red[0] + red[1] + red[2] + red[3];
-    }
-    if (sub == 0 && row >= 0 && (LANES <= 64 || threadIdx.x == 0)) {
-      if (A.mode == 1) {
-        A.partial[row] = acc;
-      } else if (A.mode == 2) {
-        A.partial[row] += acc;
-      } else {
-        if (A.mode == 3) acc += A.partial[row];
-        const float newr = (float)((double)A.base_term + (double)A.damping * acc);
-        const int64_t gv = A.row_base + row;
-        A.rank_new[gv] = newr;
-        A.contrib_new[gv] = newr * A.inv_outdeg[gv];
-        if (A.delta_max) {  // old-rank read only paid when Linf is tracked
-          const float d = fabsf(newr - A.rank_old[gv]);
-          if (d > maxd) maxd = d;
-        }
-      }
-    }
-    if constexpr (LANES > 64) __syncthreads();
-  }
+      });
   return maxd;
 }
 
 __global__ void __launch_bounds__(kBlock) k_pr_sweep(PrArgs A) {
-  const int64_t b = blockIdx.x;
-  int sec = 3;
-  if (b < A.goff[1]) sec = 0;
-  else if (b < A.goff[2]) sec = 1;
-  else if (b < A.goff[3]) sec = 2;
-  const int64_t bis = b - A.goff[sec];
-
-  float maxd;
-  switch (sec) {
-    case 0: maxd = pr_rows<4>(A, 0, bis); break;
-    case 1: maxd = pr_rows<16>(A, 1, bis); break;
-    case 2: maxd = pr_rows<64>(A, 2, bis); break;
-    default: maxd = pr_rows<256>(A, 3, bis); break;
-  }
-
+  float maxd = 0.0f;
+  for_bin_section(A.bins.goff, [&](auto lanes, int sec, int64_t bis) {
+    maxd = pr_rows<decltype(lanes)::value>(A, sec, bis);
+  });
   if (A.delta_max) {
     // block max -> one atomic per block (guide G12).
-    __shared__ float wmax[kBlock / 64];
-    for (int o = 32; o; o >>= 1) maxd = fmaxf(maxd, __shfl_down(maxd, o, 64));
-    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = maxd;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      float m = wmax[0];
-      for (int i = 1; i < kBlock / 64; ++i) m = fmaxf(m, wmax[i]);
-      atomicMax(A.delta_max, __float_as_uint(m));
-    }
+    block_reduce_atomic(
+        maxd, 0.0f, [](float a, float b) { return fmaxf(a, b); },
+        [&](float m) { atomicMax(A.delta_max, __float_as_uint(m)); });
   }
 }
 
@@ -207,15 +172,7 @@ __global__ void k_sum_f32(int64_t n, const float *x, double *out) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x)
     acc += (double)x[i];
-  __shared__ double red[kBlock / 64];
-  for (int o = 32; o; o >>= 1) acc += __shfl_down(acc, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0.0;
-    for (int i = 0; i < kBlock / 64; ++i) s += red[i];
-    atomicAdd(out, s);
-  }
+  block_reduce_atomic(acc, 0.0, mgx_op_add(), [&](double s) { atomicAdd(out, s); });
 }
 
 __global__ void k_pr_widen(int64_t n, const float *rank, const double *sum,
@@ -226,12 +183,6 @@ __global__ void k_pr_widen(int64_t n, const float *rank, const double *sum,
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x)
     out[order ? order[i] : i] = (double)rank[i] * inv;
-}
-
-inline int64_t grid_for(int64_t work, int64_t cap = 4096) {
-  int64_t g = (work + kBlock - 1) / kBlock;
-  if (g < 1) g = 1;
-  return g > cap ? cap : g;
 }
 
 mgx_status queue_one_iteration(mgx_pagerank_run *run, bool track_delta) {
@@ -278,16 +229,7 @@ mgx_status queue_one_iteration(mgx_pagerank_run *run, bool track_delta) {
     MGX_HIP_TRY(hipEventRecord(run->ev_start[run->ev_used], ctx->stream));
     for (int sIdx = 0; sIdx < n_stripes; ++sIdx) {
       const mgx_bins &bins = n_stripes == 1 ? g->bins_in : g->stripe_bins[sIdx];
-      int64_t off = 0, goff = 0;
-      for (int b = 0; b < 4; ++b) {
-        A.n[b] = bins.count[b];
-        A.off[b] = off;
-        off += A.n[b];
-        A.goff[b] = goff;
-        A.grid[b] = bins.grid[b];
-        goff += A.grid[b];
-      }
-      A.bin_rows = bins.rows;
+      const int64_t goff = mgx_fill_sections(bins, &A.bins);
       if (n_stripes == 1) {
         A.sp_lo = g->in_row_ptr;
         A.sp_hi = g->in_row_ptr + 1;

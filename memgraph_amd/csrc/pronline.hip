@@ -36,18 +36,11 @@
 #include <vector>
 
 #include "../../include/mgx_graphgen.h"
-#include "mgx_internal.h"
+#include "mgx_device.h"
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr uint32_t kMaxSteps = 1u << 20;
-
-inline int64_t grid_for(int64_t work, int64_t cap = 4096) {
-  int64_t g = (work + kBlock - 1) / kBlock;
-  if (g < 1) g = 1;
-  return g > cap ? cap : g;
-}
 
 struct PrOnlineState {
   // host slot map: memgraph id -> slot (stable across graph changes)
@@ -228,15 +221,8 @@ __global__ void k_sum_u32(int64_t n, const uint32_t *x, unsigned long long *out)
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x)
     acc += x[i];
-  __shared__ unsigned long long red[kBlock / 64];
-  for (int o = 32; o; o >>= 1) acc += __shfl_down(acc, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long s = 0;
-    for (int i = 0; i < kBlock / 64; ++i) s += red[i];
-    atomicAdd(out, s);
-  }
+  block_reduce_atomic(acc, 0ull, mgx_op_add(),
+                      [&](unsigned long long s) { atomicAdd(out, s); });
 }
 
 __global__ void k_rank_out(int64_t V, const int32_t *dense2slot, const uint32_t *counter,
