@@ -11,8 +11,23 @@
 // per-step edge quantum.
 //
 // stdin/argv: sim <row_ptr.bin u32[V+1]> <col.bin i32[E]> <V> [--no-colstream]
+//            [--xcd-affine [--granule N] [--min-degree D]]
+//            [--l2-bytes N] [--l3-bytes N] [binprefix]
 // Outputs fabric (L2-miss) and HBM (L3-miss) gather bytes per sweep, plus
 // stream traffic accounting.
+//
+// --xcd-affine models the XCD-striped sweep (memory layout lever
+// 4) on a hot-first sorted graph: for rows of in-degree >= D (default 64) a
+// gather of vertex c goes to the L2 of stripe (c / N) % 8 (N = granule in
+// vertices, a multiple of 16, default 16 = one 64-B line) whichever block
+// issues it; rows below D keep the block's own XCD. Inside a stripe's L2 the
+// line is indexed by its rank within the stripe, (c / N / 8) * (N / 16) +
+// (c % N) / 16, i.e. line >> 3 at N = 16. It must NOT be indexed by the
+// global line number: line & 7 would then pick the XCD and also be the low
+// bits of the set index, so each L2 would use one eighth of its sets and the
+// mode would show a false null (the first attempt did: 2.31 GB -> 2.25 GB at
+// RMAT-22). --l2-bytes / --l3-bytes scale the caches with a smaller graph
+// (RMAT-22: 256 KiB / 16 MiB, RMAT-24: 1 MiB / 64 MiB).
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -75,13 +90,20 @@ typedef struct {
 } Block;
 
 int main(int argc, char **argv) {
-  if (argc < 4) { fprintf(stderr, "usage: sim row_ptr.bin col.bin V [--no-colstream] [binprefix]\n"); return 2; }
-  int colstream = 1;
+  if (argc < 4) { fprintf(stderr, "usage: sim row_ptr.bin col.bin V [--no-colstream] [--xcd-affine [--granule N] [--min-degree D]] [--l2-bytes N] [--l3-bytes N] [binprefix]\n"); return 2; }
+  int colstream = 1, xcd_affine = 0;
+  long granule = 16, min_degree = 64, l2_bytes = 4l << 20, l3_bytes = 256l << 20;
   const char *binprefix = NULL;
   for (int a = 4; a < argc; ++a) {
     if (!strcmp(argv[a], "--no-colstream")) colstream = 0;
+    else if (!strcmp(argv[a], "--xcd-affine")) xcd_affine = 1;
+    else if (!strcmp(argv[a], "--granule") && a + 1 < argc) granule = atol(argv[++a]);
+    else if (!strcmp(argv[a], "--min-degree") && a + 1 < argc) min_degree = atol(argv[++a]);
+    else if (!strcmp(argv[a], "--l2-bytes") && a + 1 < argc) l2_bytes = atol(argv[++a]);
+    else if (!strcmp(argv[a], "--l3-bytes") && a + 1 < argc) l3_bytes = atol(argv[++a]);
     else binprefix = argv[a];
   }
+  if (granule < 16 || granule % 16) { fprintf(stderr, "--granule: a multiple of 16\n"); return 2; }
   long V = atol(argv[3]);
   FILE *f = fopen(argv[1], "rb");
   uint32_t *row_ptr = malloc((V + 1) * 4);
@@ -141,8 +163,8 @@ int main(int argc, char **argv) {
     }
 
   Cache l2[8], l3;
-  for (int x = 0; x < 8; ++x) cache_init(&l2[x], 4l << 20, 16);
-  cache_init(&l3, 256l << 20, 16);
+  for (int x = 0; x < 8; ++x) cache_init(&l2[x], l2_bytes, 16);
+  cache_init(&l3, l3_bytes, 16);
   uint64_t col_fabric = 0;  // col-stream lines through L2 (nt = L2-served)
 
   const long QUANTUM = 2048;  // edges per block per scheduling step
@@ -168,9 +190,18 @@ int main(int argc, char **argv) {
           uint32_t s = row_ptr[r] + B->cur_col, e = row_ptr[r + 1];
           uint32_t take = e - s;
           if ((long)take > budget) take = (uint32_t)budget;
+          const int affine = xcd_affine && (long)(row_ptr[r + 1] - row_ptr[r]) >= min_degree;
           for (uint32_t j = s; j < s + take; ++j) {
             uint64_t line = (uint64_t)(col[j] >> 4);
-            if (!cache_access(&l2[xcd], line)) cache_access(&l3, line);
+            if (affine) {
+              // the stripe's own L2, indexed by the line's rank in the stripe
+              const uint64_t q = (uint64_t)col[j] / (uint64_t)granule;
+              const uint64_t local = (q >> 3) * (uint64_t)(granule / 16) +
+                                     ((uint64_t)col[j] % (uint64_t)granule) / 16;
+              if (!cache_access(&l2[q & 7], local)) cache_access(&l3, line);
+            } else if (!cache_access(&l2[xcd], line)) {
+              cache_access(&l3, line);
+            }
             if (colstream) {
               // col stream: 16 cols per 64-B line, sequential; model only
               // the line-granular fetch into the same L2 (pollution)
@@ -207,6 +238,7 @@ int main(int argc, char **argv) {
   double vertex_gb = V * 20.0 / 1e9;
   printf("V=%ld E=%ld blocks=%ld bins=[%ld,%ld,%ld,%ld]\n", V, E, nblocks,
          cnt[0], cnt[1], cnt[2], cnt[3]);
+  if (xcd_affine) printf("xcd-affine: granule=%ld min_degree=%ld\n", granule, min_degree);
   printf("L2: hits=%llu misses=%llu hit_rate=%.3f\n",
          (unsigned long long)l2h, (unsigned long long)l2m,
          (double)l2h / (double)(l2h + l2m));

@@ -102,6 +102,9 @@ int64_t mgx_graph_local_edges(const mgx_graph *g);
 /* Device CSR build time (COO->CSR + degree bins), ms (the "CSR build ms"
  * component of BASELINE.json's metric). */
 double mgx_graph_build_ms(const mgx_graph *g);
+/* Heavy rows that PageRank sweeps XCD-striped (memory layout
+ * lever 4), or -1 when the graph was not built in that layout. */
+int64_t mgx_graph_xcd_heavy_rows(const mgx_graph *g);
 
 /* ---- PageRank (replaces pagerank_alg::ParallelIterativePageRank,
  *      algorithm/pagerank.cpp:194-242, and the pagerank.so module path) --- */

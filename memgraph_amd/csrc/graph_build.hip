@@ -13,6 +13,7 @@
 
 #include "../../include/mgx_graphgen.h"
 #include "mgx_device.h"
+#include "mgx_xcd_deal.h"
 
 namespace {
 
@@ -402,13 +403,112 @@ __global__ void k_stripe_search(int64_t rows, const uint32_t *row_ptr, const int
     out[r] = lo;
   }
 }
+
+// The 9 XCD-stripe boundaries of every heavy row: out[x*nH + slot] is the
+// first col of row H[slot] whose source id is >= off[x] (off[0] = 0 and
+// off[8] = V give the row's own start and end).
+__global__ void k_xcd_search(int64_t nH, const int32_t *H, const uint32_t *row_ptr,
+                             const int32_t *col, int64_t V, uint32_t *out) {
+  for (int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; s < nH;
+       s += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t r = H[s];
+    const uint32_t end = row_ptr[r + 1];
+    uint32_t lo = row_ptr[r];
+    out[s] = lo;
+    for (int x = 1; x < kXcdStripes; ++x) {
+      const int32_t boundary = (int32_t)mgx_xcd_stripe_off(V, x);
+      uint32_t hi = end;  // boundaries ascend: resume from the previous one
+      while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (col[mid] < boundary) lo = mid + 1;
+        else hi = mid;
+      }
+      out[(size_t)x * nH + s] = lo;
+    }
+    out[(size_t)kXcdStripes * nH + s] = end;
+  }
+}
+
+// Deal the hot-first sort to the 8 XCD stripes: position p -> id
+// mgx_xcd_deal(p, V), for the order map and the permuted out-degrees alike.
+__global__ void k_xcd_deal(int64_t n, const int32_t *order_sorted, const uint32_t *deg_sorted,
+                           int32_t *order, uint32_t *deg) {
+  for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < n;
+       p += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t id = mgx_xcd_deal(p, n);
+    order[id] = order_sorted[p];
+    deg[id] = deg_sorted[p];
+  }
+}
+
+// Heavy-row stripe view for the XCD-striped PageRank sweep (g->xcd).
+mgx_status build_xcd_view(mgx_context *ctx, mgx_graph *g) {
+  // Heavy rows are whole sections of bins_in, so the slot -> row list is the
+  // tail of bins_in.rows: MGX_PR_XCD_HEAVY_MIN is one of the bin edges.
+  int heavy_min = 64;
+  if (const char *e = getenv("MGX_PR_XCD_HEAVY_MIN")) {
+    const int v = atoi(e);
+    if (v == 8 || v == 64 || v == 1024) heavy_min = v;
+  }
+  const int sec = heavy_min == 8 ? 1 : heavy_min == 64 ? 2 : 3;
+  g->xcd_heavy_min = heavy_min;
+  g->xcd_heavy_sec = sec;
+  int64_t light = 0, nH = 0;
+  for (int b = 0; b < 4; ++b) (b < sec ? light : nH) += g->bins_in.count[b];
+  g->xcd_nH = nH;
+  if (nH == 0) return MGX_OK;
+  g->xcd_H = g->bins_in.rows + light;
+  MGX_HIP_TRY(mgx_hip_malloc(&g->xcd_ptr, (size_t)(kXcdStripes + 1) * nH * sizeof(uint32_t)));
+  hipLaunchKernelGGL(k_xcd_search, dim3(grid_for(nH)), dim3(kBlock), 0, ctx->stream, nH,
+                     g->xcd_H, g->in_row_ptr, g->in_col, g->n_vertices, g->xcd_ptr);
+  for (int x = 0; x < kXcdStripes; ++x) {
+    // Empty segments are dropped: the finish kernel skips them by comparing
+    // the two boundaries, so their partial slots are never read.
+    MGX_TRY(mgx_build_bins_range(ctx, g->xcd_ptr + (size_t)x * nH,
+                                 g->xcd_ptr + (size_t)(x + 1) * nH, nH,
+                                 /*include_zero=*/false, &g->xcd_bins[x]));
+  }
+  // The sweep picks its stripe's sections by block index: keep them on the
+  // device rather than in the kernel arguments.
+  mgx_bin_sections secs[kXcdStripes];
+  for (int x = 0; x < kXcdStripes; ++x) (void)mgx_fill_sections(g->xcd_bins[x], &secs[x]);
+  MGX_HIP_TRY(mgx_hip_malloc(&g->xcd_sec, sizeof(secs)));
+  MGX_HIP_TRY(hipMemcpyAsync(g->xcd_sec, secs, sizeof(secs), hipMemcpyHostToDevice,
+                             ctx->stream));
+  MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return MGX_OK;
+}
 }  // namespace
+
+bool mgx_xcd_wanted(int64_t n_vertices) {
+  const char *stripes = getenv("MGX_PR_STRIPES");
+  if (stripes && atoi(stripes) > 0) return false;  // the sequential stripe path
+  const char *e = getenv("MGX_PR_XCD");
+  if (e && *e) return atoi(e) != 0;
+  // Unset: on from 1.5 * 2^25 vertices. Measured per sweep against the
+  // unstriped layout (profiles/xcd_stripes.md): +6% at 2^22, +3% at 2^23,
+  // -0.7% at 2^24, -2% at 2^25, -12% at 2^26. While f32 contrib[V] sits
+  // well inside the 256 MiB Infinity Cache an L2 miss is cheap and the
+  // partials and two extra launches cost more than they save; the 2% at
+  // 2^25 does not repay the ~7 ms the view adds to the build within 20
+  // sweeps. The threshold lies between the two measured points, where
+  // contrib reaches three quarters of the Infinity Cache.
+  return n_vertices >= (int64_t)3 << 24;
+}
 
 mgx_status mgx_build_stripes(mgx_context *ctx, mgx_graph *g) {
   // Called while row_end is still the clamped row count (the sharded path
   // re-pads it afterwards), so this is exactly the in-CSR row count.
   const int64_t rows = g->row_end - g->row_begin;
   const int64_t V = g->n_vertices;
+  if (g->xcd) {
+    // XCD-affine layout: `order` is already dealt to 8 stripes, whose
+    // boundaries are the exact prefix sums off[1..7] (not x * width). Only
+    // heavy rows are striped, all 8 stripes in one launch; the sequential
+    // stripe view below stays off.
+    g->n_stripes = 1;
+    return build_xcd_view(ctx, g);
+  }
   int n_stripes = 1;
   const char *env = getenv("MGX_PR_STRIPES");
   if (env && atoi(env) > 0) {
@@ -422,7 +522,11 @@ mgx_status mgx_build_stripes(mgx_context *ctx, mgx_graph *g) {
   } else {
     // Hot-first-permuted layout: the hub prefix already keeps the gather
     // working set cache-resident; stripes only add fp64-partial traffic
-    // (measured RMAT-26: S=1 116.3 G edges/s vs S=3 106.0). Stay unstriped.
+    // (measured RMAT-26: S=1 116.3 G edges/s vs S=3 106.0: a few contiguous
+    // stripes only move lines from HBM to the Infinity Cache, and the sweep
+    // is bound by the fabric line rate per L2 miss, not by HBM). Stay
+    // unstriped; the XCD-affine view above is the striping that changes
+    // what each L2 holds.
     n_stripes = 1;
   }
   if (n_stripes > 16) n_stripes = 16;
@@ -522,11 +626,21 @@ mgx_status mgx_build_from_device_coo(mgx_context *ctx, const int32_t *d_src,
         return rocprim::radix_sort_pairs_desc(tmp, bytes, g->out_degree, deg_sorted, iota,
                                               g->order, V, 0, 32, ctx->stream);
       }));
+      g->xcd = mgx_xcd_wanted(V);
+      if (g->xcd) {
+        // XCD-affine layout: deal the sorted positions to 8 stripes
+        // (mgx_xcd_deal.h); iota is free again and holds the sorted order.
+        MGX_HIP_TRY(hipMemcpyAsync(iota, g->order, V * sizeof(int32_t),
+                                   hipMemcpyDeviceToDevice, ctx->stream));
+        hipLaunchKernelGGL(k_xcd_deal, dim3(grid_for(V)), dim3(kBlock), 0, ctx->stream, V,
+                           iota, deg_sorted, g->order, g->out_degree);
+      } else {
+        MGX_HIP_TRY(hipMemcpyAsync(g->out_degree, deg_sorted, V * sizeof(uint32_t),
+                                   hipMemcpyDeviceToDevice, ctx->stream));
+      }
+      // out_degree / inv_outdeg are now in the permuted space.
       hipLaunchKernelGGL(k_invert_perm, dim3(grid_for(V)), dim3(kBlock), 0, ctx->stream, V,
                          g->order, d_perm);
-      // out_degree / inv_outdeg move to the permuted space.
-      MGX_HIP_TRY(hipMemcpyAsync(g->out_degree, deg_sorted, V * sizeof(uint32_t),
-                                 hipMemcpyDeviceToDevice, ctx->stream));
       hipLaunchKernelGGL(k_inv_outdeg, dim3(grid_for(V)), dim3(kBlock), 0, ctx->stream, V,
                          g->out_degree, g->inv_outdeg);
       MGX_HIP_TRY(hipFree(deg_sorted));

@@ -367,6 +367,11 @@ extern "C" mgx_status mgx_graph_destroy(mgx_context *ctx, mgx_graph *g) {
   for (int i = 0; i < 16; ++i) {
     if (g->stripe_bins[i].rows) (void)hipFree(g->stripe_bins[i].rows);
   }
+  if (g->xcd_ptr) (void)hipFree(g->xcd_ptr);
+  if (g->xcd_sec) (void)hipFree(g->xcd_sec);
+  for (int i = 0; i < 8; ++i) {
+    if (g->xcd_bins[i].rows) (void)hipFree(g->xcd_bins[i].rows);
+  }
   delete g;
   return MGX_OK;
 }
@@ -375,6 +380,9 @@ extern "C" int64_t mgx_graph_num_vertices(const mgx_graph *g) { return g->n_vert
 extern "C" int64_t mgx_graph_num_edges(const mgx_graph *g) { return g->n_edges; }
 extern "C" int64_t mgx_graph_local_edges(const mgx_graph *g) { return g->in_edges; }
 extern "C" double mgx_graph_build_ms(const mgx_graph *g) { return g->build_ms; }
+extern "C" int64_t mgx_graph_xcd_heavy_rows(const mgx_graph *g) {
+  return g->xcd ? g->xcd_nH : -1;
+}
 
 extern "C" mgx_status mgx_wcc(mgx_context *ctx, mgx_graph *g, int64_t *out_component,
                               int64_t *n_components) {

@@ -42,9 +42,8 @@ inline int64_t mgx_fill_sections(const mgx_bins &bins, mgx_bin_sections *s) {
   return goff;
 }
 
-// blockIdx.x -> (section, block within the section).
-__device__ inline int bin_section(const int64_t (&goff)[4], int64_t *block_in_sec) {
-  const int64_t b = blockIdx.x;
+// Block index b of the launch -> (section, block within the section).
+__device__ inline int bin_section(const int64_t (&goff)[4], int64_t b, int64_t *block_in_sec) {
   int sec = 3;
   if (b < goff[1]) sec = 0;
   else if (b < goff[2]) sec = 1;
@@ -53,17 +52,28 @@ __device__ inline int bin_section(const int64_t (&goff)[4], int64_t *block_in_se
   return sec;
 }
 
-// Call f(lanes, sec, block_in_sec) for this block's section, where
+// blockIdx.x -> (section, block within the section).
+__device__ inline int bin_section(const int64_t (&goff)[4], int64_t *block_in_sec) {
+  return bin_section(goff, (int64_t)blockIdx.x, block_in_sec);
+}
+
+// Call f(lanes, sec, block_in_sec) for the section of block index b, where
 // decltype(lanes)::value is the section's lanes per row (4/16/64/256).
 template <typename F>
-__device__ inline void for_bin_section(const int64_t (&goff)[4], F &&f) {
+__device__ inline void for_bin_section(const int64_t (&goff)[4], int64_t b, F &&f) {
   int64_t bis;
-  switch (bin_section(goff, &bis)) {
+  switch (bin_section(goff, b, &bis)) {
     case 0: f(std::integral_constant<int, 4>{}, 0, bis); break;
     case 1: f(std::integral_constant<int, 16>{}, 1, bis); break;
     case 2: f(std::integral_constant<int, 64>{}, 2, bis); break;
     default: f(std::integral_constant<int, 256>{}, 3, bis); break;
   }
+}
+
+// The same for this block's own index.
+template <typename F>
+__device__ inline void for_bin_section(const int64_t (&goff)[4], F &&f) {
+  for_bin_section(goff, (int64_t)blockIdx.x, static_cast<F &&>(f));
 }
 
 // Grid-stride over the rows of section `sec`, kBlock/LANES rows per block per

@@ -168,6 +168,25 @@ struct mgx_graph {
   uint32_t *stripe_ptr = nullptr;          // [(n_stripes+1) * rows]
   mgx_bins stripe_bins[16];                // per stripe (max 16)
 
+  // XCD-affine striping (PageRank, permuted single-GPU layout; DESIGN.md
+  // lever 4). `order` is the hot-first sort dealt to 8 stripes in 16-vertex
+  // granules (mgx_xcd_deal.h), so stripe x is the id range [off[x], off[x+1])
+  // and is hot-first inside. Heavy rows (whole in-degree >= xcd_heavy_min:
+  // the bins_in sections from xcd_heavy_sec on) are swept in one launch whose
+  // block b gathers only stripe b & 7, so each XCD's L2 caches its own eighth
+  // of contrib; light rows keep the unstriped sweep. Slot s is heavy row
+  // xcd_H[s]; stripe x of it is the col range
+  // [xcd_ptr[x*nH + s], xcd_ptr[(x+1)*nH + s]). xcd_bins[x] lists the slots
+  // with a non-empty stripe-x segment, binned by segment length.
+  bool xcd = false;
+  int xcd_heavy_min = 0;
+  int xcd_heavy_sec = 4;
+  int64_t xcd_nH = 0;
+  const int32_t *xcd_H = nullptr;  // [nH], a view into bins_in.rows (not owned)
+  uint32_t *xcd_ptr = nullptr;     // [9 * nH]
+  mgx_bins xcd_bins[8];
+  struct mgx_bin_sections *xcd_sec = nullptr;  // [8] device: xcd_bins as launch sections
+
   double build_ms = 0.0;
 };
 
@@ -189,8 +208,14 @@ mgx_status mgx_build_bins(mgx_context *ctx, const uint32_t *row_ptr, int64_t row
 mgx_status mgx_build_bins_range(mgx_context *ctx, const uint32_t *lo, const uint32_t *hi,
                                 int64_t rows, bool include_zero, mgx_bins *bins);
 // Source-stripe the (sorted) in-CSR of g; n_stripes chosen from V (env
-// MGX_PR_STRIPES overrides; 1 = disabled).
+// MGX_PR_STRIPES overrides; 1 = disabled). When g->xcd is set (decided
+// before the renumbering, see mgx_xcd_wanted) it builds the heavy-row XCD
+// stripe view instead and leaves n_stripes at 1.
 mgx_status mgx_build_stripes(mgx_context *ctx, mgx_graph *g);
+// Whether a permuted single-GPU build of V vertices takes the XCD-affine
+// layout: MGX_PR_XCD=1/0 forces it on/off for any V, MGX_PR_STRIPES set
+// disables it, and unset it is on for V >= 1.5 * 2^25 (measured threshold).
+bool mgx_xcd_wanted(int64_t n_vertices);
 
 // Sharded in-CSR build: keeps only edges with dst in [row_begin,row_end);
 // out_degree stays global.
@@ -209,7 +234,10 @@ struct mgx_pagerank_run {
   int cur = 0;
   uint32_t *d_delta = nullptr;  // Linf as ordered-uint f32
   double *d_scratch = nullptr;  // sum + f64 output [V+1]
-  double *d_partial = nullptr;  // striped sweep: fp64 row partials [rows]
+  // fp64 row partials: [rows] for the sequential striped sweep, [8 * nH]
+  // (stripe-major) for the XCD-striped one.
+  double *d_partial = nullptr;
+  int xcd_grid = 0;  // XCD-striped launch: resident grid, a multiple of 8
   int64_t iterations = 0;
   // HIP-event timing of the sweep kernel (the dominant kernel).
   std::vector<hipEvent_t> ev_start, ev_stop;

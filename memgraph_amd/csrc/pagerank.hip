@@ -9,12 +9,18 @@
 // the per-block Linf(delta) into a device scalar — so per-iteration traffic
 // is the algorithmic 8 B/edge + ~20 B/vertex (DESIGN.md roofline).
 //
+// Large permuted graphs take the XCD-affine layout instead (mgx_graph::xcd,
+// DESIGN.md "Memory layout levers" item 4): the heavy rows in one launch
+// whose blocks each gather from one eighth of contrib, the light rows in the
+// fused kernel above, and a finish kernel over the heavy rows.
+//
 // Parity bar (tests/test_gpu_pagerank.py): |r_gpu - r_cpu|inf <= 1e-6 vs the
 // fp64 oracle after equal iterations, post sum-normalize.
 
 #include <chrono>
 
 #include "mgx_device.h"
+#include "mgx_xcd_deal.h"
 
 namespace {
 
@@ -39,7 +45,6 @@ struct PrArgs {
   const uint32_t *sp_hi;
   double *partial;
   int mode;
-  int deep;  // experiment: 4x-unrolled wide path (16 gathers/lane in flight)
 };
 
 // This lane's share of sum_{u->row} contrib[u] over the row's stripe range.
@@ -60,26 +65,6 @@ __device__ inline double pr_row_sum(const PrArgs &A, int32_t row, int sub) {
     typedef int v4i __attribute__((ext_vector_type(4)));
     const v4i *col4 = reinterpret_cast<const v4i *>(A.col + s_al);
     uint32_t c = sub;
-    if (A.deep) {
-      // 4x unrolled: 16 independent gathers in flight per lane
-      // (MGX_PR_DEEP_UNROLL experiment).
-      for (; c + 3 * LANES < nvec; c += 4 * LANES) {
-        const v4i c0 = __builtin_nontemporal_load(col4 + c);
-        const v4i c1 = __builtin_nontemporal_load(col4 + c + LANES);
-        const v4i c2 = __builtin_nontemporal_load(col4 + c + 2 * LANES);
-        const v4i c3 = __builtin_nontemporal_load(col4 + c + 3 * LANES);
-        float g[16];
-        g[0] = A.contrib_old[c0.x]; g[1] = A.contrib_old[c0.y];
-        g[2] = A.contrib_old[c0.z]; g[3] = A.contrib_old[c0.w];
-        g[4] = A.contrib_old[c1.x]; g[5] = A.contrib_old[c1.y];
-        g[6] = A.contrib_old[c1.z]; g[7] = A.contrib_old[c1.w];
-        g[8] = A.contrib_old[c2.x]; g[9] = A.contrib_old[c2.y];
-        g[10] = A.contrib_old[c2.z]; g[11] = A.contrib_old[c2.w];
-        g[12] = A.contrib_old[c3.x]; g[13] = A.contrib_old[c3.y];
-        g[14] = A.contrib_old[c3.z]; g[15] = A.contrib_old[c3.w];
-        for (int k = 0; k < 16; ++k) acc += (double)g[k];
-      }
-    }
     // 2x unrolled: 8 independent gathers in flight per lane.
     for (; c + LANES < nvec; c += 2 * LANES) {
       const v4i c0 = __builtin_nontemporal_load(col4 + c);
@@ -119,6 +104,26 @@ __device__ inline double pr_row_sum(const PrArgs &A, int32_t row, int sub) {
   return acc;
 }
 
+// Row epilogue from the row's fp64 gather sum: new rank, new contrib, and
+// this thread's running Linf(new - old) when that is tracked.
+__device__ inline void pr_finish_row(const PrArgs &A, int32_t row, double acc, float &maxd) {
+  const float newr = (float)((double)A.base_term + (double)A.damping * acc);
+  const int64_t gv = A.row_base + row;
+  A.rank_new[gv] = newr;
+  A.contrib_new[gv] = newr * A.inv_outdeg[gv];
+  if (A.delta_max) {  // old-rank read only paid when Linf is tracked
+    const float d = fabsf(newr - A.rank_old[gv]);
+    if (d > maxd) maxd = d;
+  }
+}
+
+// Block max of the per-thread Linf -> one atomic per block (guide G12).
+__device__ inline void pr_fold_delta(const PrArgs &A, float maxd) {
+  block_reduce_atomic(
+      maxd, 0.0f, [](float a, float b) { return fmaxf(a, b); },
+      [&](float m) { atomicMax(A.delta_max, __float_as_uint(m)); });
+}
+
 template <int LANES>
 __device__ inline float pr_rows(const PrArgs &A, int sec, int64_t block_in_sec) {
   float maxd = 0.0f;
@@ -132,14 +137,7 @@ __device__ inline float pr_rows(const PrArgs &A, int sec, int64_t block_in_sec) 
           A.partial[row] += acc;
         } else {
           if (A.mode == 3) acc += A.partial[row];
-          const float newr = (float)((double)A.base_term + (double)A.damping * acc);
-          const int64_t gv = A.row_base + row;
-          A.rank_new[gv] = newr;
-          A.contrib_new[gv] = newr * A.inv_outdeg[gv];
-          if (A.delta_max) {  // old-rank read only paid when Linf is tracked
-            const float d = fabsf(newr - A.rank_old[gv]);
-            if (d > maxd) maxd = d;
-          }
+          pr_finish_row(A, row, acc, maxd);
         }
       });
   return maxd;
@@ -150,12 +148,68 @@ __global__ void __launch_bounds__(kBlock) k_pr_sweep(PrArgs A) {
   for_bin_section(A.bins.goff, [&](auto lanes, int sec, int64_t bis) {
     maxd = pr_rows<decltype(lanes)::value>(A, sec, bis);
   });
-  if (A.delta_max) {
-    // block max -> one atomic per block (guide G12).
-    block_reduce_atomic(
-        maxd, 0.0f, [](float a, float b) { return fmaxf(a, b); },
-        [&](float m) { atomicMax(A.delta_max, __float_as_uint(m)); });
+  if (A.delta_max) pr_fold_delta(A, maxd);
+}
+
+// XCD-striped sweep over the heavy rows (mgx_graph::xcd). Block b gathers
+// only from source stripe b & 7 and acts as block b >> 3 of that stripe's
+// bin sections (rows are slots here), so the blocks that share an XCD — b
+// and b + 8 under the observed round-robin dispatch — share one eighth of
+// contrib and the eight L2s hold eight different slices. The grid is
+// resident at once and strides over the stripe's section blocks, so that
+// placement does not depend on redispatch order. Each segment's fp64 sum
+// goes to partial[x * nH + slot]; k_pr_finish_heavy combines them. No
+// block reads what another wrote: a different placement changes the speed
+// only.
+struct PrXcdArgs {
+  const int32_t *col;
+  const float *contrib_old;
+  double *partial;                // [8 * nH], stripe-major
+  const mgx_bin_sections *sec;    // [8] device: stripe x's sections over slots
+  const uint32_t *xptr;           // [9 * nH] stripe boundaries by slot
+  int64_t nH;
+};
+
+__global__ void __launch_bounds__(kBlock) k_pr_sweep_xcd(PrXcdArgs X) {
+  const int x = blockIdx.x % kXcdStripes;
+  const mgx_bin_sections &S = X.sec[x];
+  PrArgs A;  // only what pr_row_sum reads
+  A.col = X.col;
+  A.contrib_old = X.contrib_old;
+  A.sp_lo = X.xptr + (size_t)x * X.nH;
+  A.sp_hi = A.sp_lo + X.nH;
+  double *out = X.partial + (size_t)x * X.nH;
+  const int64_t vgrid = S.goff[3] + S.grid[3];
+  const int64_t stride = gridDim.x / kXcdStripes;
+  for (int64_t vb = blockIdx.x / kXcdStripes; vb < vgrid; vb += stride) {
+    for_bin_section(S.goff, vb, [&](auto lanes, int sec, int64_t bis) {
+      constexpr int L = decltype(lanes)::value;
+      reduce_bin_rows<L>(
+          S, sec, bis, 0.0, mgx_op_add(),
+          [&](int32_t slot, int sub) { return pr_row_sum<L>(A, slot, sub); },
+          [&](int32_t slot, double acc) { out[slot] = acc; });
+    });
   }
+}
+
+// Heavy rows: sum the 8 stripe partials in stripe order and finish the row.
+// A stripe whose segment is empty (equal boundaries) wrote no partial and is
+// skipped, so no stale slot is read.
+__global__ void __launch_bounds__(kBlock)
+k_pr_finish_heavy(PrArgs A, const int32_t *H, const uint32_t *xptr, int64_t nH) {
+  float maxd = 0.0f;
+  for (int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; s < nH;
+       s += (int64_t)gridDim.x * blockDim.x) {
+    double acc = 0.0;
+    uint32_t lo = xptr[s];
+    for (int x = 0; x < kXcdStripes; ++x) {
+      const uint32_t hi = xptr[(size_t)(x + 1) * nH + s];
+      if (hi > lo) acc += A.partial[(size_t)x * nH + s];
+      lo = hi;
+    }
+    pr_finish_row(A, H[s], acc, maxd);
+  }
+  if (A.delta_max) pr_fold_delta(A, maxd);
 }
 
 __global__ void k_pr_init(int64_t n, float r0, const float *inv, float *rank,
@@ -185,6 +239,40 @@ __global__ void k_pr_widen(int64_t n, const float *rank, const double *sum,
     out[order ? order[i] : i] = (double)rank[i] * inv;
 }
 
+// One sweep of the XCD-affine layout: the heavy rows' striped launch into the
+// partials, the plain sweep over the light rows (the bins_in sections below
+// the heavy ones), then the heavy rows' finish.
+mgx_status queue_xcd_sweep(mgx_pagerank_run *run, PrArgs A) {
+  mgx_context *ctx = run->ctx;
+  mgx_graph *g = run->g;
+  const int64_t nH = g->xcd_nH;
+  if (nH > 0) {
+    PrXcdArgs X;
+    X.col = g->in_col;
+    X.contrib_old = A.contrib_old;
+    X.partial = run->d_partial;
+    X.sec = g->xcd_sec;
+    X.xptr = g->xcd_ptr;
+    X.nH = nH;
+    hipLaunchKernelGGL(k_pr_sweep_xcd, dim3((uint32_t)run->xcd_grid), dim3(kBlock), 0,
+                       ctx->stream, X);
+  }
+  mgx_bins light = g->bins_in;
+  for (int b = g->xcd_heavy_sec; b < 4; ++b) light.count[b] = light.grid[b] = 0;
+  const int64_t goff = mgx_fill_sections(light, &A.bins);
+  A.sp_lo = g->in_row_ptr;
+  A.sp_hi = g->in_row_ptr + 1;
+  A.mode = 0;
+  if (goff > 0) {
+    hipLaunchKernelGGL(k_pr_sweep, dim3((uint32_t)goff), dim3(kBlock), 0, ctx->stream, A);
+  }
+  if (nH > 0) {
+    hipLaunchKernelGGL(k_pr_finish_heavy, dim3((uint32_t)grid_for(nH)), dim3(kBlock), 0,
+                       ctx->stream, A, g->xcd_H, (const uint32_t *)g->xcd_ptr, nH);
+  }
+  return MGX_OK;
+}
+
 mgx_status queue_one_iteration(mgx_pagerank_run *run, bool track_delta) {
   mgx_context *ctx = run->ctx;
   mgx_graph *g = run->g;
@@ -203,13 +291,6 @@ mgx_status queue_one_iteration(mgx_pagerank_run *run, bool track_delta) {
   A.damping = (float)run->damping;
   A.delta_max = track_delta ? run->d_delta : nullptr;
   A.partial = run->d_partial;
-  {
-    static const int deep = [] {
-      const char *e = getenv("MGX_PR_DEEP_UNROLL");
-      return e && atoi(e) ? 1 : 0;
-    }();
-    A.deep = deep;
-  }
 
   if (track_delta) MGX_HIP_TRY(hipMemsetAsync(run->d_delta, 0, 4, ctx->stream));
 
@@ -218,7 +299,8 @@ mgx_status queue_one_iteration(mgx_pagerank_run *run, bool track_delta) {
   const int64_t rows = (g->row_end < V ? g->row_end : V) - g->row_begin;
   if (V > 0) {
     // Event-bracket the whole per-iteration sweep group (1 launch when
-    // unstriped, n_stripes launches otherwise): feeds roofline.achieved.
+    // unstriped, n_stripes launches when striped, heavy + light + finish in
+    // the XCD-affine layout): feeds roofline.achieved.
     if (run->ev_used >= (int64_t)run->ev_start.size()) {
       hipEvent_t e0, e1;
       MGX_HIP_TRY(hipEventCreate(&e0));
@@ -227,21 +309,25 @@ mgx_status queue_one_iteration(mgx_pagerank_run *run, bool track_delta) {
       run->ev_stop.push_back(e1);
     }
     MGX_HIP_TRY(hipEventRecord(run->ev_start[run->ev_used], ctx->stream));
-    for (int sIdx = 0; sIdx < n_stripes; ++sIdx) {
-      const mgx_bins &bins = n_stripes == 1 ? g->bins_in : g->stripe_bins[sIdx];
-      const int64_t goff = mgx_fill_sections(bins, &A.bins);
-      if (n_stripes == 1) {
-        A.sp_lo = g->in_row_ptr;
-        A.sp_hi = g->in_row_ptr + 1;
-        A.mode = 0;
-      } else {
-        A.sp_lo = g->stripe_ptr + (size_t)sIdx * rows;
-        A.sp_hi = g->stripe_ptr + (size_t)(sIdx + 1) * rows;
-        A.mode = sIdx == 0 ? 1 : (sIdx == n_stripes - 1 ? 3 : 2);
-      }
-      if (goff > 0) {
-        hipLaunchKernelGGL(k_pr_sweep, dim3((uint32_t)goff), dim3(kBlock), 0, ctx->stream,
-                           A);
+    if (g->xcd) {
+      MGX_TRY(queue_xcd_sweep(run, A));
+    } else {
+      for (int sIdx = 0; sIdx < n_stripes; ++sIdx) {
+        const mgx_bins &bins = n_stripes == 1 ? g->bins_in : g->stripe_bins[sIdx];
+        const int64_t goff = mgx_fill_sections(bins, &A.bins);
+        if (n_stripes == 1) {
+          A.sp_lo = g->in_row_ptr;
+          A.sp_hi = g->in_row_ptr + 1;
+          A.mode = 0;
+        } else {
+          A.sp_lo = g->stripe_ptr + (size_t)sIdx * rows;
+          A.sp_hi = g->stripe_ptr + (size_t)(sIdx + 1) * rows;
+          A.mode = sIdx == 0 ? 1 : (sIdx == n_stripes - 1 ? 3 : 2);
+        }
+        if (goff > 0) {
+          hipLaunchKernelGGL(k_pr_sweep, dim3((uint32_t)goff), dim3(kBlock), 0, ctx->stream,
+                             A);
+        }
       }
     }
     MGX_HIP_TRY(hipEventRecord(run->ev_stop[run->ev_used], ctx->stream));
@@ -362,6 +448,24 @@ mgx_status pagerank_start_common(mgx_context *ctx, mgx_graph *g, double damping,
   if (g->n_stripes > 1) {
     const int64_t rows = (dist ? (row_end < V ? row_end : V) : V) - row_begin;
     MGX_TRY(ctx->alloc_async((void **)&run->d_partial, rows * sizeof(double)));
+  }
+  if (g->xcd && g->xcd_nH > 0) {
+    MGX_TRY(ctx->alloc_async((void **)&run->d_partial,
+                             (size_t)kXcdStripes * g->xcd_nH * sizeof(double)));
+    // A grid that is resident at once (occupancy x CUs, a multiple of 8), no
+    // larger than the busiest stripe's sections need.
+    int per_cu = 0, cus = 0;
+    MGX_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pr_sweep_xcd, kBlock, 0));
+    MGX_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    int64_t want = 0;
+    for (int x = 0; x < kXcdStripes; ++x) {
+      const int64_t vg = g->xcd_bins[x].total_grid();
+      if (vg > want) want = vg;
+    }
+    int64_t per_stripe = (int64_t)per_cu * cus / kXcdStripes;
+    if (per_stripe > want) per_stripe = want;
+    if (per_stripe < 1) per_stripe = 1;
+    run->xcd_grid = (int)(per_stripe * kXcdStripes);
   }
   if (V > 0) {
     const float r0 = (float)(1.0 / (double)V);

@@ -66,6 +66,7 @@ class Native:
         self.lib.mgx_graph_num_vertices.restype = ctypes.c_int64
         self.lib.mgx_graph_num_edges.restype = ctypes.c_int64
         self.lib.mgx_graph_local_edges.restype = ctypes.c_int64
+        self.lib.mgx_graph_xcd_heavy_rows.restype = ctypes.c_int64
 
     def _check(self, status, what):
         if status != 0:
@@ -142,6 +143,10 @@ class Native:
 
     def graph_build_ms(self, g):
         return self.lib.mgx_graph_build_ms(g)
+
+    def graph_xcd_heavy_rows(self, g):
+        """Rows PageRank sweeps XCD-striped, or -1 when that layout is off."""
+        return self.lib.mgx_graph_xcd_heavy_rows(g)
 
     # --- algorithms ---
     def pagerank(self, ctx, g, n_vertices, max_iterations=100, damping=0.85, eps=1e-5):
