@@ -181,6 +181,44 @@ mgx_status mgx_bfs(mgx_context *ctx, mgx_graph *g, int64_t source, int directed,
                    int64_t *out_hops /* nullable */, int64_t *out_parent /* nullable */,
                    mgx_bfs_stats *stats /* nullable */);
 
+/* ---- Node similarity: Jaccard and overlap of out-neighbour sets (replaces
+ *      node_similarity_algs::CalculateSimilarityPairwise / ...Cartesian,
+ *      src/mage/cpp/node_similarity_module/algorithms/node_similarity.hpp
+ *      :126-200) -----------------------------------------------------------
+ * The set of u is the distinct `to` ids of its out-edges (GetNeighbors,
+ * node_similarity.hpp:107-121): a self-loop puts u in its own set, multi-
+ * edges count once. u == v is legal (1.0, or 0.0 for an empty set). Needs
+ * MGX_BUILD_OUT_CSR; ids are original vertex ids. The first call builds a
+ * deduplicated view of the out-CSR and caches it on the graph.
+ * The quotient is one fp64 IEEE division of two integers, as in the
+ * reference, so results are bit-identical to it. */
+#define MGX_SIM_JACCARD 0   /* |A∩B| / |A∪B|, 0 when the union is empty   (node_similarity.hpp:43-52) */
+#define MGX_SIM_OVERLAP 1   /* |A∩B| / min(|A|,|B|), 0 when that min is 0 (node_similarity.hpp:59-68) */
+#define MGX_SIM_AUTO   0    /* per pair: SEARCH when s*ceil(log2(l+1)) < s+l, else MERGE */
+#define MGX_SIM_SEARCH 1    /* every pair by binary search of the longer row */
+#define MGX_SIM_MERGE  2    /* every pair by tiled merge */
+typedef struct {
+  int64_t pairs, search_pairs, merge_pairs;
+  int64_t distinct_entries;   /* size of the deduplicated out-neighbour view */
+  int64_t chunks;             /* all-pairs: device->host chunks */
+  double prep_ms, ms;         /* HIP events; ms excludes prep and download */
+} mgx_similarity_stats;
+/* n_pairs >= 2^31 => MGX_ERR_TOO_LARGE; n_pairs == 0 => MGX_OK, nothing
+ * written. */
+mgx_status mgx_similarity_pairs(mgx_context *ctx, mgx_graph *g, int metric, int mode,
+                                const int64_t *u, const int64_t *v, int64_t n_pairs,
+                                double *out_sim /* [n_pairs] */,
+                                int64_t *out_common /* nullable */,
+                                mgx_similarity_stats *stats /* nullable */);
+/* Every pair i < j, zeros included, pair (i, j) at i*(2V-i-1)/2 + (j-i-1):
+ * the order CalculateSimilarityCartesian emits for scan-order ids.
+ * V >= 65537 (>= 2^31 pairs) => MGX_ERR_TOO_LARGE. Results leave the device
+ * in chunks of whole rows i, at most MGX_SIM_CHUNK_PAIRS (default 2^27,
+ * 1 GiB) pairs each. */
+mgx_status mgx_similarity_all(mgx_context *ctx, mgx_graph *g, int metric,
+                              double *out_sim /* [V(V-1)/2] */,
+                              mgx_similarity_stats *stats /* nullable */);
+
 /* ---- Katz (replaces katz_alg::SetKatz, katz.cpp:393-414) ---------------
  * Needs IN_CSR. Convergence rule replicates Converged (katz.cpp:165-215)
  * after the k-override, incl. divergent-series IEEE behavior. */

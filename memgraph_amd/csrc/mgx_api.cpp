@@ -372,6 +372,11 @@ extern "C" mgx_status mgx_graph_destroy(mgx_context *ctx, mgx_graph *g) {
   for (int i = 0; i < 8; ++i) {
     if (g->xcd_bins[i].rows) (void)hipFree(g->xcd_bins[i].rows);
   }
+  if (!g->uniq_alias) {
+    if (g->uniq_row_ptr) (void)hipFree(g->uniq_row_ptr);
+    if (g->uniq_col) (void)hipFree(g->uniq_col);
+  }
+  if (g->uniq_bins.rows) (void)hipFree(g->uniq_bins.rows);
   delete g;
   return MGX_OK;
 }
@@ -395,6 +400,21 @@ extern "C" mgx_status mgx_bfs(mgx_context *ctx, mgx_graph *g, int64_t source, in
                               int64_t *out_parent, mgx_bfs_stats *stats) {
   MGX_HIP_TRY(hipSetDevice(ctx->device));
   return mgx_bfs_impl(ctx, g, source, directed, max_depth, mode, out_hops, out_parent, stats);
+}
+
+extern "C" mgx_status mgx_similarity_pairs(mgx_context *ctx, mgx_graph *g, int metric,
+                                           int mode, const int64_t *u, const int64_t *v,
+                                           int64_t n_pairs, double *out_sim,
+                                           int64_t *out_common, mgx_similarity_stats *stats) {
+  MGX_HIP_TRY(hipSetDevice(ctx->device));
+  return mgx_similarity_pairs_impl(ctx, g, metric, mode, u, v, n_pairs, out_sim, out_common,
+                                   stats);
+}
+
+extern "C" mgx_status mgx_similarity_all(mgx_context *ctx, mgx_graph *g, int metric,
+                                         double *out_sim, mgx_similarity_stats *stats) {
+  MGX_HIP_TRY(hipSetDevice(ctx->device));
+  return mgx_similarity_all_impl(ctx, g, metric, out_sim, stats);
 }
 
 extern "C" mgx_status mgx_katz(mgx_context *ctx, mgx_graph *g, double alpha, double epsilon,

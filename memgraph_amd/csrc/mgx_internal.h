@@ -187,6 +187,17 @@ struct mgx_graph {
   mgx_bins xcd_bins[8];
   struct mgx_bin_sections *xcd_sec = nullptr;  // [8] device: xcd_bins as launch sections
 
+  // Deduplicated view of the out-CSR (similarity.hip), built at the first
+  // similarity call. When the out-CSR has no repeated (src, dst) both
+  // pointers alias out_row_ptr / out_col (uniq_alias) and own nothing.
+  // uniq_bins: rows of the view with entries, for the all-pairs sweep.
+  uint32_t *uniq_row_ptr = nullptr;
+  int32_t *uniq_col = nullptr;
+  int64_t uniq_entries = 0;
+  bool uniq_alias = false;
+  mgx_bins uniq_bins;
+  bool uniq_bins_built = false;
+
   double build_ms = 0.0;
 };
 
@@ -272,6 +283,14 @@ mgx_status mgx_betweenness_impl(mgx_context *ctx, mgx_graph *g, int directed, in
 mgx_status mgx_bfs_impl(mgx_context *ctx, mgx_graph *g, int64_t source, int directed,
                         int64_t max_depth, int mode, int64_t *out_hops, int64_t *out_parent,
                         mgx_bfs_stats *stats);
+
+// similarity.hip
+mgx_status mgx_similarity_pairs_impl(mgx_context *ctx, mgx_graph *g, int metric, int mode,
+                                     const int64_t *u, const int64_t *v, int64_t n_pairs,
+                                     double *out_sim, int64_t *out_common,
+                                     mgx_similarity_stats *stats);
+mgx_status mgx_similarity_all_impl(mgx_context *ctx, mgx_graph *g, int metric, double *out_sim,
+                                   mgx_similarity_stats *stats);
 
 // comm.cpp (RCCL)
 mgx_status mgx_comm_allgather_f32(mgx_context *ctx, const float *send, float *recv,

@@ -257,6 +257,41 @@ inline void EmitNodeRecord(mgp_graph *graph, mgp_result *result, mgp_memory *mem
   insert_value(record);
 }
 
+// The same for records that carry two nodes (node_similarity's
+// (node1, node2, similarity) rows): both vertices are resolved before the
+// record is created, so a missing one never leaves a half-filled row.
+template <typename InsertValue>
+inline void EmitNodePairRecord(mgp_graph *graph, mgp_result *result, mgp_memory *memory,
+                               int64_t mg_id1, const char *node1_field, int64_t mg_id2,
+                               const char *node2_field, InsertValue &&insert_value) {
+  mgp_vertex *v1 = nullptr, *v2 = nullptr;
+  enum mgp_error e1 = mgp_graph_get_vertex_by_id(graph, mgp_vertex_id{mg_id1}, memory, &v1);
+  enum mgp_error e2 = mgp_graph_get_vertex_by_id(graph, mgp_vertex_id{mg_id2}, memory, &v2);
+  if (e1 != MGP_ERROR_NO_ERROR || e2 != MGP_ERROR_NO_ERROR || !v1 || !v2) {
+    if (v1) mgp_vertex_destroy(v1);
+    if (v2) mgp_vertex_destroy(v2);
+    int transactional = 1;
+    Check(mgp_graph_is_transactional(graph, &transactional), "graph_is_transactional");
+    if (transactional) throw MgpError("invalid vertex id during result emission");
+    return;
+  }
+  mgp_value *val1 = nullptr, *val2 = nullptr;
+  Check(mgp_value_make_vertex(v1, &val1), "value_make_vertex");
+  if (mgp_value_make_vertex(v2, &val2) != MGP_ERROR_NO_ERROR) {
+    mgp_value_destroy(val1);
+    mgp_vertex_destroy(v2);
+    throw MgpError("value_make_vertex failed");
+  }
+  mgp_result_record *record = nullptr;
+  enum mgp_error re = mgp_result_new_record(result, &record);
+  if (re == MGP_ERROR_NO_ERROR) re = mgp_result_record_insert(record, node1_field, val1);
+  if (re == MGP_ERROR_NO_ERROR) re = mgp_result_record_insert(record, node2_field, val2);
+  mgp_value_destroy(val1);
+  mgp_value_destroy(val2);
+  Check(re, "record_insert(node pair)");
+  insert_value(record);
+}
+
 inline void InsertDouble(mgp_result_record *record, const char *field, double v,
                          mgp_memory *memory) {
   mgp_value *val = nullptr;

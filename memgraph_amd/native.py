@@ -51,6 +51,25 @@ class BfsStats(ctypes.Structure):
     ]
 
 
+SIM_JACCARD = 0
+SIM_OVERLAP = 1
+SIM_AUTO = 0
+SIM_SEARCH = 1
+SIM_MERGE = 2
+
+
+class SimilarityStats(ctypes.Structure):
+    _fields_ = [
+        ("pairs", ctypes.c_int64),
+        ("search_pairs", ctypes.c_int64),
+        ("merge_pairs", ctypes.c_int64),
+        ("distinct_entries", ctypes.c_int64),
+        ("chunks", ctypes.c_int64),
+        ("prep_ms", ctypes.c_double),
+        ("ms", ctypes.c_double),
+    ]
+
+
 class MgxError(RuntimeError):
     pass
 
@@ -218,6 +237,45 @@ class Native:
                                                       max_depth, mode, want_parent)
         self._check(status, "mgx_bfs")
         return hops, parent, stats
+
+    def similarity_pairs_status(self, ctx, g, u, v, metric, mode=SIM_AUTO):
+        """Raw call: (status, sim, common, stats) without raising."""
+        u = np.ascontiguousarray(u, dtype=np.int64)
+        v = np.ascontiguousarray(v, dtype=np.int64)
+        assert u.shape == v.shape and u.ndim == 1
+        n = len(u)
+        sim = np.full(n, np.nan, dtype=np.float64)
+        common = np.full(n, -1, dtype=np.int64)
+        stats = SimilarityStats()
+        status = self.lib.mgx_similarity_pairs(ctx, g, ctypes.c_int(metric),
+                                               ctypes.c_int(mode), u.ctypes.data_as(_I64),
+                                               v.ctypes.data_as(_I64), ctypes.c_int64(n),
+                                               sim.ctypes.data_as(_F64),
+                                               common.ctypes.data_as(_I64),
+                                               ctypes.byref(stats))
+        return status, sim, common, stats
+
+    def similarity_pairs(self, ctx, g, u, v, metric, mode=SIM_AUTO):
+        status, sim, common, stats = self.similarity_pairs_status(ctx, g, u, v, metric, mode)
+        self._check(status, "mgx_similarity_pairs")
+        return sim, common, stats
+
+    def similarity_all_status(self, ctx, g, n_vertices, metric):
+        """Raw call: (status, sim_or_None, stats); nothing is sized when the
+        pair count is out of range (the library refuses before writing)."""
+        stats = SimilarityStats()
+        sim = None
+        if 0 <= n_vertices <= 65536:
+            sim = np.full(n_vertices * (n_vertices - 1) // 2, np.nan, dtype=np.float64)
+        status = self.lib.mgx_similarity_all(ctx, g, ctypes.c_int(metric),
+                                             sim.ctypes.data_as(_F64) if sim is not None
+                                             else None, ctypes.byref(stats))
+        return status, sim, stats
+
+    def similarity_all(self, ctx, g, n_vertices, metric):
+        status, sim, stats = self.similarity_all_status(ctx, g, n_vertices, metric)
+        self._check(status, "mgx_similarity_all")
+        return sim, stats
 
     def katz(self, ctx, g, n_vertices, alpha=0.2, epsilon=1e-2):
         out = np.zeros(n_vertices, dtype=np.float64)
