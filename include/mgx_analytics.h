@@ -102,6 +102,9 @@ int64_t mgx_graph_local_edges(const mgx_graph *g);
 /* Device CSR build time (COO->CSR + degree bins), ms (the "CSR build ms"
  * component of BASELINE.json's metric). */
 double mgx_graph_build_ms(const mgx_graph *g);
+/* Rows of the in-CSR with no in-edges, which the steady-state PageRank sweep
+ * leaves out (0 when the graph has no in-CSR). */
+int64_t mgx_graph_in_zero_rows(const mgx_graph *g);
 /* Heavy rows that PageRank sweeps XCD-striped (memory layout
  * lever 4), or -1 when the graph was not built in that layout. */
 int64_t mgx_graph_xcd_heavy_rows(const mgx_graph *g);
@@ -140,6 +143,9 @@ mgx_status mgx_pagerank_iterate(mgx_pagerank_run *run, int64_t n_iterations);
  * same iteration count (no collective divergence). */
 mgx_status mgx_pagerank_iterate_eps(mgx_pagerank_run *run, int64_t max_n,
                                     double stop_epsilon, int64_t *done);
+/* Floats of each XCD stripe's hot prefix that this run's striped launch keeps
+ * in LDS per block (MGX_PR_XCD_LDS, or the automatic size); 0 = no table. */
+int64_t mgx_pagerank_xcd_lds_floats(const mgx_pagerank_run *run);
 /* Sweep timing accumulated so far (ms) and launch count. */
 mgx_status mgx_pagerank_timing(mgx_pagerank_run *run, double *sweep_ms, int64_t *launches);
 mgx_status mgx_pagerank_finish(mgx_pagerank_run *run, double *out_rank /* nullable */);

@@ -81,25 +81,27 @@ __global__ void k_bin_keys(int64_t rows, const uint32_t *lo, const uint32_t *hi,
   for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < rows;
        r += (int64_t)gridDim.x * blockDim.x) {
     const uint32_t deg = hi[r] - lo[r];
-    uint32_t k = deg < 8 ? 0u : deg < 64 ? 1u : deg < 1024 ? 2u : 3u;
-    if (deg == 0 && !include_zero) k = 4u;  // dropped (sorts last)
+    // 0 = zero-degree rows (a section of their own in front of bin0),
+    // 1..4 = the four bins, 5 = dropped (sorts last).
+    uint32_t k = deg < 8 ? 1u : deg < 64 ? 2u : deg < 1024 ? 3u : 4u;
+    if (deg == 0) k = include_zero ? 0u : 5u;
     keys[r] = k;
     vals[r] = (uint32_t)r;
   }
 }
 
-__global__ void k_count_bins(int64_t rows, const uint32_t *keys, uint32_t *counts5) {
+__global__ void k_count_bins(int64_t rows, const uint32_t *keys, uint32_t *counts6) {
   // Per-block LDS aggregation first: a naive global histogram measured
-  // 706 ms at RMAT-26 (atomic hotspot); this form is ~ms. Key 4 counts the
-  // dropped zero-degree rows.
-  __shared__ uint32_t local[5];
-  if (threadIdx.x < 5) local[threadIdx.x] = 0;
+  // 706 ms at RMAT-26 (atomic hotspot); this form is ~ms. Key 0 counts the
+  // kept zero-degree rows, key 5 the dropped ones.
+  __shared__ uint32_t local[6];
+  if (threadIdx.x < 6) local[threadIdx.x] = 0;
   __syncthreads();
   for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < rows;
        r += (int64_t)gridDim.x * blockDim.x)
     atomicAdd(&local[keys[r]], 1u);
   __syncthreads();
-  if (threadIdx.x < 5 && local[threadIdx.x]) atomicAdd(&counts5[threadIdx.x], local[threadIdx.x]);
+  if (threadIdx.x < 6 && local[threadIdx.x]) atomicAdd(&counts6[threadIdx.x], local[threadIdx.x]);
 }
 
 __global__ void k_pack_pairs(int64_t n_edges, const int32_t *src, const int32_t *dst,
@@ -345,40 +347,37 @@ mgx_status mgx_build_bins_range(mgx_context *ctx, const uint32_t *lo, const uint
   MGX_HIP_TRY(mgx_hip_malloc(&keys, rows * sizeof(uint32_t)));
   MGX_HIP_TRY(mgx_hip_malloc(&keys_out, rows * sizeof(uint32_t)));
   MGX_HIP_TRY(mgx_hip_malloc(&vals, rows * sizeof(uint32_t)));
-  uint32_t *counts5 = nullptr;
-  MGX_HIP_TRY(mgx_hip_malloc(&counts5, 5 * sizeof(uint32_t)));
-  MGX_HIP_TRY(hipMemsetAsync(counts5, 0, 20, ctx->stream));
+  uint32_t *counts6 = nullptr;
+  MGX_HIP_TRY(mgx_hip_malloc(&counts6, 6 * sizeof(uint32_t)));
+  MGX_HIP_TRY(hipMemsetAsync(counts6, 0, 24, ctx->stream));
 
   hipLaunchKernelGGL(k_bin_keys, dim3(grid_for(rows)), dim3(kBlock), 0, ctx->stream, rows,
                      lo, hi, include_zero ? 1 : 0, keys, vals);
   hipLaunchKernelGGL(k_count_bins, dim3(grid_for(rows)), dim3(kBlock), 0, ctx->stream, rows,
-                     keys, counts5);
+                     keys, counts6);
 
-  // Stable 3-bit radix sort: within a bin, rows stay in ascending id order;
-  // key 4 (dropped rows) lands past the used prefix.
+  // Stable 3-bit radix sort: within a bin, rows stay in ascending id order,
+  // the zero-degree rows (key 0) ahead of bin0's others; key 5 (dropped rows)
+  // lands past the used prefix.
   MGX_TRY(mgx_with_temp(ctx, "degree-bin sort", [&](void *tmp, size_t &bytes) {
     return rocprim::radix_sort_pairs(tmp, bytes, keys, keys_out, vals,
                                      (uint32_t *)bins->rows, rows, 0, 3, ctx->stream);
   }));
 
-  uint32_t h_counts[5] = {0, 0, 0, 0, 0};
-  MGX_HIP_TRY(hipMemcpyAsync(h_counts, counts5, 20, hipMemcpyDeviceToHost, ctx->stream));
+  uint32_t h_counts[6] = {0, 0, 0, 0, 0, 0};
+  MGX_HIP_TRY(hipMemcpyAsync(h_counts, counts6, 24, hipMemcpyDeviceToHost, ctx->stream));
   MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  for (int b = 0; b < 4; ++b) bins->count[b] = h_counts[b];
-
-  // Launch geometry: rows-per-block {64,16,4,1}; grid-stride caps keep the
-  // dispatch bounded (guide G11) while >> 256 CUs stay fed.
-  const int64_t rows_per_block[4] = {64, 16, 4, 1};
-  const int64_t cap[4] = {2048, 2048, 2048, 8192};
-  for (int b = 0; b < 4; ++b) {
-    int64_t need = (bins->count[b] + rows_per_block[b] - 1) / rows_per_block[b];
-    bins->grid[b] = bins->count[b] ? (need < cap[b] ? need : cap[b]) : 0;
-  }
+  // Consumers see bin0 as before: the zero-degree rows and the rows of
+  // degree 1..7 from offset 0.
+  bins->n_zero = h_counts[0];
+  bins->count[0] = (int64_t)h_counts[0] + h_counts[1];
+  for (int b = 1; b < 4; ++b) bins->count[b] = h_counts[b + 1];
+  for (int b = 0; b < 4; ++b) bins->grid[b] = mgx_bin_grid(b, bins->count[b]);
 
   MGX_HIP_TRY(hipFree(keys));
   MGX_HIP_TRY(hipFree(keys_out));
   MGX_HIP_TRY(hipFree(vals));
-  MGX_HIP_TRY(hipFree(counts5));
+  MGX_HIP_TRY(hipFree(counts6));
   return MGX_OK;
 }
 

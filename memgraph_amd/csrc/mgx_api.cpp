@@ -385,6 +385,7 @@ extern "C" int64_t mgx_graph_num_vertices(const mgx_graph *g) { return g->n_vert
 extern "C" int64_t mgx_graph_num_edges(const mgx_graph *g) { return g->n_edges; }
 extern "C" int64_t mgx_graph_local_edges(const mgx_graph *g) { return g->in_edges; }
 extern "C" double mgx_graph_build_ms(const mgx_graph *g) { return g->build_ms; }
+extern "C" int64_t mgx_graph_in_zero_rows(const mgx_graph *g) { return g->bins_in.n_zero; }
 extern "C" int64_t mgx_graph_xcd_heavy_rows(const mgx_graph *g) {
   return g->xcd ? g->xcd_nH : -1;
 }

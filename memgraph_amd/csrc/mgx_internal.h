@@ -111,10 +111,23 @@ struct mgx_context {
 struct mgx_bins {
   int32_t *rows = nullptr;  // [n_rows] device: bin0 rows, then bin1, ...
   int64_t count[4] = {0, 0, 0, 0};
+  // The first n_zero rows of bin0 (counted in count[0]) are the rows of degree
+  // 0, when the list includes them: a sweep that has nothing to do for such
+  // rows starts bin0 past them.
+  int64_t n_zero = 0;
   // Launch geometry (computed host-side at build).
   int64_t grid[4] = {0, 0, 0, 0};
   int64_t total_grid() const { return grid[0] + grid[1] + grid[2] + grid[3]; }
 };
+
+// Blocks for `count` rows of bin b: rows-per-block {64,16,4,1}; grid-stride
+// caps keep the dispatch bounded (guide G11) while >> 256 CUs stay fed.
+inline int64_t mgx_bin_grid(int b, int64_t count) {
+  const int64_t rows_per_block[4] = {64, 16, 4, 1};
+  const int64_t cap[4] = {2048, 2048, 2048, 8192};
+  const int64_t need = (count + rows_per_block[b] - 1) / rows_per_block[b];
+  return count ? (need < cap[b] ? need : cap[b]) : 0;
+}
 
 struct mgx_graph {
   int64_t n_vertices = 0;
@@ -215,7 +228,7 @@ mgx_status mgx_gen_weights_device(mgx_context *ctx, int64_t n_edges, uint64_t se
 mgx_status mgx_build_bins(mgx_context *ctx, const uint32_t *row_ptr, int64_t rows,
                           mgx_bins *bins);
 // Degree-bin work lists from explicit per-row [lo, hi) ranges; rows with
-// zero degree are dropped unless include_zero.
+// zero degree are dropped unless include_zero, and then lead bin0 (n_zero).
 mgx_status mgx_build_bins_range(mgx_context *ctx, const uint32_t *lo, const uint32_t *hi,
                                 int64_t rows, bool include_zero, mgx_bins *bins);
 // Source-stripe the (sorted) in-CSR of g; n_stripes chosen from V (env
@@ -249,6 +262,12 @@ struct mgx_pagerank_run {
   // (stripe-major) for the XCD-striped one.
   double *d_partial = nullptr;
   int xcd_grid = 0;  // XCD-striped launch: resident grid, a multiple of 8
+  // XCD-striped launch: floats of each stripe's hot prefix held in LDS per
+  // block (0 = none), chosen when the run starts (MGX_PR_XCD_LDS).
+  int64_t xcd_lds_floats = 0;
+  // Rows of in-degree 0 leave the sweep from the third iteration on
+  // (MGX_PR_SKIP_ZERO=0 keeps them in).
+  bool skip_zero = true;
   int64_t iterations = 0;
   // HIP-event timing of the sweep kernel (the dominant kernel).
   std::vector<hipEvent_t> ev_start, ev_stop;

@@ -12,7 +12,10 @@
 // Large permuted graphs take the XCD-affine layout instead (mgx_graph::xcd,
 // DESIGN.md "Memory layout levers" item 4): the heavy rows in one launch
 // whose blocks each gather from one eighth of contrib, the light rows in the
-// fused kernel above, and a finish kernel over the heavy rows.
+// fused kernel above, and a finish kernel over the heavy rows. The striped
+// launch keeps the hottest sources of its stripe in LDS (lever 5). From a
+// run's third sweep on, the rows of in-degree 0 are left out: both ping-pong
+// buffers already hold their values.
 //
 // Parity bar (tests/test_gpu_pagerank.py): |r_gpu - r_cpu|inf <= 1e-6 vs the
 // fp64 oracle after equal iterations, post sum-normalize.
@@ -47,9 +50,33 @@ struct PrArgs {
   int mode;
 };
 
-// This lane's share of sum_{u->row} contrib[u] over the row's stripe range.
-template <int LANES>
-__device__ inline double pr_row_sum(const PrArgs &A, int32_t row, int sub) {
+// How a sweep reads contrib[c]. The plain global gather: the fused sweep and
+// the striped launch without an LDS table.
+struct PrLoadGlobal {
+  static constexpr bool kFlat = false;
+  const float *contrib;
+  __device__ float operator()(int32_t c) const { return contrib[c]; }
+};
+
+// The striped launch with its stripe's hot prefix in LDS (DESIGN.md lever 5):
+// hot[0 .. kx) holds contrib[base .. base + kx), the same bits, so a gather
+// served from it adds the same value. The select of the two addresses
+// compiles to one flat load per gather, no branch.
+struct PrLoadHot {
+  static constexpr bool kFlat = true;
+  const float *contrib;
+  const float *hot;
+  uint32_t base, kx;
+  __device__ float operator()(int32_t c) const {
+    const uint32_t r = (uint32_t)c - base;
+    return r < kx ? hot[r] : contrib[c];
+  }
+};
+
+// This lane's share of sum_{u->row} contrib[u] over the row's stripe range;
+// load(c) reads contrib[c].
+template <int LANES, typename Load>
+__device__ inline double pr_row_sum(const PrArgs &A, int32_t row, int sub, Load load) {
   double acc = 0.0;
   const uint32_t s = A.sp_lo[row], e = A.sp_hi[row];
   if constexpr (LANES >= 64) {
@@ -60,23 +87,31 @@ __device__ inline double pr_row_sum(const PrArgs &A, int32_t row, int sub) {
     uint32_t s_al = (s + 3u) & ~3u;
     if (s_al > e) s_al = e;
     for (uint32_t j = s + sub; j < s_al; j += LANES)
-      acc += (double)A.contrib_old[A.col[j]];
+      acc += (double)load(A.col[j]);
     const uint32_t nvec = (e - s_al) / 4;
     typedef int v4i __attribute__((ext_vector_type(4)));
     const v4i *col4 = reinterpret_cast<const v4i *>(A.col + s_al);
     uint32_t c = sub;
     // 2x unrolled: 8 independent gathers in flight per lane.
     for (; c + LANES < nvec; c += 2 * LANES) {
-      const v4i c0 = __builtin_nontemporal_load(col4 + c);
-      const v4i c1 = __builtin_nontemporal_load(col4 + c + LANES);
-      const float g0 = A.contrib_old[c0.x];
-      const float g1 = A.contrib_old[c0.y];
-      const float g2 = A.contrib_old[c0.z];
-      const float g3 = A.contrib_old[c0.w];
-      const float g4 = A.contrib_old[c1.x];
-      const float g5 = A.contrib_old[c1.y];
-      const float g6 = A.contrib_old[c1.z];
-      const float g7 = A.contrib_old[c1.w];
+      v4i c0 = __builtin_nontemporal_load(col4 + c);
+      v4i c1 = __builtin_nontemporal_load(col4 + c + LANES);
+      if constexpr (Load::kFlat) {
+        // Flat loads return out of order, so once one is pending the wait
+        // for c1 becomes vmcnt(0) and drains the gathers issued before it,
+        // four in flight instead of eight. Have both column vectors arrive
+        // before the first gather.
+        asm volatile("" : "+v"(c0.x), "+v"(c0.y), "+v"(c0.z), "+v"(c0.w), "+v"(c1.x),
+                     "+v"(c1.y), "+v"(c1.z), "+v"(c1.w));
+      }
+      const float g0 = load(c0.x);
+      const float g1 = load(c0.y);
+      const float g2 = load(c0.z);
+      const float g3 = load(c0.w);
+      const float g4 = load(c1.x);
+      const float g5 = load(c1.y);
+      const float g6 = load(c1.z);
+      const float g7 = load(c1.w);
       acc += (double)g0;
       acc += (double)g1;
       acc += (double)g2;
@@ -88,18 +123,18 @@ __device__ inline double pr_row_sum(const PrArgs &A, int32_t row, int sub) {
     }
     for (; c < nvec; c += LANES) {
       const v4i cc = __builtin_nontemporal_load(col4 + c);
-      acc += (double)A.contrib_old[cc.x];
-      acc += (double)A.contrib_old[cc.y];
-      acc += (double)A.contrib_old[cc.z];
-      acc += (double)A.contrib_old[cc.w];
+      acc += (double)load(cc.x);
+      acc += (double)load(cc.y);
+      acc += (double)load(cc.z);
+      acc += (double)load(cc.w);
     }
     for (uint32_t j = s_al + nvec * 4 + sub; j < e; j += LANES)
-      acc += (double)A.contrib_old[A.col[j]];
+      acc += (double)load(A.col[j]);
   } else {
     // Short rows: a LANES-wide group reads consecutive cols (16/64-B
     // granules); nt keeps the one-pass col stream out of L1.
     row_gather<LANES>(A.col, s, e, sub,
-                      [&](int32_t c) { acc += (double)A.contrib_old[c]; });
+                      [&](int32_t c) { acc += (double)load(c); });
   }
   return acc;
 }
@@ -129,7 +164,9 @@ __device__ inline float pr_rows(const PrArgs &A, int sec, int64_t block_in_sec) 
   float maxd = 0.0f;
   reduce_bin_rows<LANES>(
       A.bins, sec, block_in_sec, 0.0, mgx_op_add(),
-      [&](int32_t row, int sub) { return pr_row_sum<LANES>(A, row, sub); },
+      [&](int32_t row, int sub) {
+        return pr_row_sum<LANES>(A, row, sub, PrLoadGlobal{A.contrib_old});
+      },
       [&](int32_t row, double acc) {
         if (A.mode == 1) {
           A.partial[row] = acc;
@@ -168,27 +205,49 @@ struct PrXcdArgs {
   const mgx_bin_sections *sec;    // [8] device: stripe x's sections over slots
   const uint32_t *xptr;           // [9 * nH] stripe boundaries by slot
   int64_t nH;
+  int64_t V;
+  uint32_t hot_k;                 // HOT: floats of dynamic LDS per block
 };
 
-__global__ void __launch_bounds__(kBlock) k_pr_sweep_xcd(PrXcdArgs X) {
+// HOT: the block first copies the hottest min(hot_k, stripe length) sources of
+// its stripe, contrib_old[off[x] ..), into LDS and gathers those from there.
+// The stripe is hot-first inside, so that prefix takes the largest share of
+// the gathers a table of this size can; contrib_old is read-only for the
+// whole launch. Every gathered value has the same bits either way.
+// The two 64-bit flat addresses per gather would take HOT to 78 VGPRs and 6
+// waves per SIMD; it is held to the 7-wave step the plain launch has (70).
+template <bool HOT>
+__global__ void __launch_bounds__(kBlock, HOT ? 7 : 1) k_pr_sweep_xcd(PrXcdArgs X) {
   const int x = blockIdx.x % kXcdStripes;
   const mgx_bin_sections &S = X.sec[x];
   PrArgs A;  // only what pr_row_sum reads
   A.col = X.col;
-  A.contrib_old = X.contrib_old;
   A.sp_lo = X.xptr + (size_t)x * X.nH;
   A.sp_hi = A.sp_lo + X.nH;
   double *out = X.partial + (size_t)x * X.nH;
   const int64_t vgrid = S.goff[3] + S.grid[3];
   const int64_t stride = gridDim.x / kXcdStripes;
-  for (int64_t vb = blockIdx.x / kXcdStripes; vb < vgrid; vb += stride) {
-    for_bin_section(S.goff, vb, [&](auto lanes, int sec, int64_t bis) {
-      constexpr int L = decltype(lanes)::value;
-      reduce_bin_rows<L>(
-          S, sec, bis, 0.0, mgx_op_add(),
-          [&](int32_t slot, int sub) { return pr_row_sum<L>(A, slot, sub); },
-          [&](int32_t slot, double acc) { out[slot] = acc; });
-    });
+  auto sweep = [&](auto load) {
+    for (int64_t vb = blockIdx.x / kXcdStripes; vb < vgrid; vb += stride) {
+      for_bin_section(S.goff, vb, [&](auto lanes, int sec, int64_t bis) {
+        constexpr int L = decltype(lanes)::value;
+        reduce_bin_rows<L>(
+            S, sec, bis, 0.0, mgx_op_add(),
+            [&](int32_t slot, int sub) { return pr_row_sum<L>(A, slot, sub, load); },
+            [&](int32_t slot, double acc) { out[slot] = acc; });
+      });
+    }
+  };
+  if constexpr (HOT) {
+    extern __shared__ float hot[];
+    const int64_t base = mgx_xcd_stripe_off(X.V, x);
+    const int64_t len = mgx_xcd_stripe_off(X.V, x + 1) - base;
+    const uint32_t kx = len < (int64_t)X.hot_k ? (uint32_t)len : X.hot_k;
+    for (uint32_t i = threadIdx.x; i < kx; i += kBlock) hot[i] = X.contrib_old[base + i];
+    __syncthreads();
+    sweep(PrLoadHot{X.contrib_old, hot, (uint32_t)base, kx});
+  } else {
+    sweep(PrLoadGlobal{X.contrib_old});
   }
 }
 
@@ -239,6 +298,24 @@ __global__ void k_pr_widen(int64_t n, const float *rank, const double *sum,
     out[order ? order[i] : i] = (double)rank[i] * inv;
 }
 
+// The launch sections of `bins` for this sweep of the run; returns the total
+// grid. From the third sweep on, a row of in-degree 0 would be given the
+// values it already holds in both ping-pong buffers (rank base_term, contrib
+// base_term * inv_outdeg, Linf contribution 0), so bin0 then starts past
+// those rows and its grid is sized for the rest.
+int64_t pr_fill_sections(const mgx_pagerank_run *run, const mgx_bins &bins,
+                         mgx_bin_sections *s) {
+  const int64_t nz = bins.n_zero;
+  if (!run->skip_zero || run->dist || run->iterations < 2 || nz == 0)
+    return mgx_fill_sections(bins, s);
+  mgx_bins rest = bins;
+  rest.count[0] -= nz;
+  rest.grid[0] = mgx_bin_grid(0, rest.count[0]);
+  const int64_t goff = mgx_fill_sections(rest, s);
+  for (int b = 0; b < 4; ++b) s->off[b] += nz;
+  return goff;
+}
+
 // One sweep of the XCD-affine layout: the heavy rows' striped launch into the
 // partials, the plain sweep over the light rows (the bins_in sections below
 // the heavy ones), then the heavy rows' finish.
@@ -254,12 +331,19 @@ mgx_status queue_xcd_sweep(mgx_pagerank_run *run, PrArgs A) {
     X.sec = g->xcd_sec;
     X.xptr = g->xcd_ptr;
     X.nH = nH;
-    hipLaunchKernelGGL(k_pr_sweep_xcd, dim3((uint32_t)run->xcd_grid), dim3(kBlock), 0,
-                       ctx->stream, X);
+    X.V = g->n_vertices;
+    X.hot_k = (uint32_t)run->xcd_lds_floats;
+    if (X.hot_k > 0) {
+      hipLaunchKernelGGL(k_pr_sweep_xcd<true>, dim3((uint32_t)run->xcd_grid), dim3(kBlock),
+                         (size_t)X.hot_k * sizeof(float), ctx->stream, X);
+    } else {
+      hipLaunchKernelGGL(k_pr_sweep_xcd<false>, dim3((uint32_t)run->xcd_grid), dim3(kBlock), 0,
+                         ctx->stream, X);
+    }
   }
   mgx_bins light = g->bins_in;
   for (int b = g->xcd_heavy_sec; b < 4; ++b) light.count[b] = light.grid[b] = 0;
-  const int64_t goff = mgx_fill_sections(light, &A.bins);
+  const int64_t goff = pr_fill_sections(run, light, &A.bins);
   A.sp_lo = g->in_row_ptr;
   A.sp_hi = g->in_row_ptr + 1;
   A.mode = 0;
@@ -314,7 +398,10 @@ mgx_status queue_one_iteration(mgx_pagerank_run *run, bool track_delta) {
     } else {
       for (int sIdx = 0; sIdx < n_stripes; ++sIdx) {
         const mgx_bins &bins = n_stripes == 1 ? g->bins_in : g->stripe_bins[sIdx];
-        const int64_t goff = mgx_fill_sections(bins, &A.bins);
+        // Only the single launch (mode 0) may leave the zero-degree rows out:
+        // the sequential stripes finish every row from its partial.
+        const int64_t goff = n_stripes == 1 ? pr_fill_sections(run, bins, &A.bins)
+                                            : mgx_fill_sections(bins, &A.bins);
         if (n_stripes == 1) {
           A.sp_lo = g->in_row_ptr;
           A.sp_hi = g->in_row_ptr + 1;
@@ -421,6 +508,64 @@ mgx_status mgx_pagerank_normalize_download(mgx_pagerank_run *run, double *out_ra
 
 namespace {
 
+// Resident blocks per CU of the striped launch with `floats` of dynamic LDS.
+mgx_status xcd_blocks_per_cu(int64_t floats, int *per_cu) {
+  if (floats > 0) {
+    MGX_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+        per_cu, k_pr_sweep_xcd<true>, kBlock, (size_t)floats * sizeof(float)));
+  } else {
+    MGX_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k_pr_sweep_xcd<false>,
+                                                             kBlock, 0));
+  }
+  return MGX_OK;
+}
+
+// Floats of each stripe's hot prefix that the striped launch keeps in LDS
+// (run->xcd_lds_floats), chosen per run. MGX_PR_XCD_LDS=<floats> forces it
+// (0 = the launch without a table), clamped to the longest stripe and to what
+// one block may allocate. Unset: the largest multiple of 256 floats that
+// leaves the occupancy query's blocks per CU where they are with no dynamic
+// LDS; a larger table trades resident waves for LDS hits, which measured
+// slower (profiles/lds_hot_prefix.md).
+mgx_status pick_xcd_lds(mgx_pagerank_run *run) {
+  const int64_t V = run->g->n_vertices;
+  int64_t longest = 0;
+  for (int x = 0; x < kXcdStripes; ++x) {
+    const int64_t len = mgx_xcd_stripe_off(V, x + 1) - mgx_xcd_stripe_off(V, x);
+    if (len > longest) longest = len;
+  }
+  hipFuncAttributes fa;
+  MGX_HIP_TRY(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k_pr_sweep_xcd<true>)));
+  int block_lds = 0;
+  MGX_HIP_TRY(hipDeviceGetAttribute(&block_lds, hipDeviceAttributeMaxSharedMemoryPerBlock,
+                                    run->ctx->device));
+  const int64_t most = ((int64_t)block_lds - (int64_t)fa.sharedSizeBytes) / (int64_t)sizeof(float);
+  int64_t k = 0;
+  const char *e = getenv("MGX_PR_XCD_LDS");
+  if (e && *e) {
+    k = atoll(e);
+    if (k < 0) k = 0;
+  } else {
+    constexpr int64_t kStep = 256;
+    int base_blocks = 0;
+    MGX_TRY(xcd_blocks_per_cu(0, &base_blocks));
+    int64_t lo = 0, hi = most / kStep;  // steps: lo keeps the occupancy, above hi does not fit
+    while (lo < hi) {
+      const int64_t mid = (lo + hi + 1) / 2;
+      int blocks = 0;
+      MGX_TRY(xcd_blocks_per_cu(mid * kStep, &blocks));
+      if (blocks >= base_blocks) lo = mid;
+      else hi = mid - 1;
+    }
+    k = lo * kStep;
+  }
+  if (k > longest) k = longest;
+  if (k > most) k = most;
+  if (k < 0) k = 0;
+  run->xcd_lds_floats = k;
+  return MGX_OK;
+}
+
 mgx_status pagerank_start_common(mgx_context *ctx, mgx_graph *g, double damping,
                                  bool dist, int64_t row_begin, int64_t row_end,
                                  mgx_pagerank_run **out) {
@@ -435,6 +580,7 @@ mgx_status pagerank_start_common(mgx_context *ctx, mgx_graph *g, double damping,
   run->dist = dist;
   run->row_begin = row_begin;
   run->row_end = row_end;
+  if (const char *e = getenv("MGX_PR_SKIP_ZERO")) run->skip_zero = !(*e && atoi(e) == 0);
   const int64_t V = g->n_vertices;
   // Distributed rank/contrib arrays are padded to world*shard.
   const int64_t alloc = dist ? (row_end - row_begin) * (int64_t)mgx_comm_world(ctx) : V;
@@ -452,10 +598,11 @@ mgx_status pagerank_start_common(mgx_context *ctx, mgx_graph *g, double damping,
   if (g->xcd && g->xcd_nH > 0) {
     MGX_TRY(ctx->alloc_async((void **)&run->d_partial,
                              (size_t)kXcdStripes * g->xcd_nH * sizeof(double)));
+    MGX_TRY(pick_xcd_lds(run));
     // A grid that is resident at once (occupancy x CUs, a multiple of 8), no
     // larger than the busiest stripe's sections need.
     int per_cu = 0, cus = 0;
-    MGX_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pr_sweep_xcd, kBlock, 0));
+    MGX_TRY(xcd_blocks_per_cu(run->xcd_lds_floats, &per_cu));
     MGX_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
     int64_t want = 0;
     for (int x = 0; x < kXcdStripes; ++x) {
@@ -525,6 +672,10 @@ extern "C" mgx_status mgx_pagerank_iterate_eps(mgx_pagerank_run *run, int64_t ma
   }
   if (done) *done = i;
   return MGX_OK;
+}
+
+extern "C" int64_t mgx_pagerank_xcd_lds_floats(const mgx_pagerank_run *run) {
+  return run->xcd_lds_floats;
 }
 
 extern "C" mgx_status mgx_pagerank_timing(mgx_pagerank_run *run, double *sweep_ms,

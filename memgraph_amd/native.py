@@ -86,6 +86,8 @@ class Native:
         self.lib.mgx_graph_num_edges.restype = ctypes.c_int64
         self.lib.mgx_graph_local_edges.restype = ctypes.c_int64
         self.lib.mgx_graph_xcd_heavy_rows.restype = ctypes.c_int64
+        self.lib.mgx_graph_in_zero_rows.restype = ctypes.c_int64
+        self.lib.mgx_pagerank_xcd_lds_floats.restype = ctypes.c_int64
 
     def _check(self, status, what):
         if status != 0:
@@ -167,6 +169,10 @@ class Native:
         """Rows PageRank sweeps XCD-striped, or -1 when that layout is off."""
         return self.lib.mgx_graph_xcd_heavy_rows(g)
 
+    def graph_in_zero_rows(self, g):
+        """Rows with no in-edges, left out of the steady-state PageRank sweep."""
+        return self.lib.mgx_graph_in_zero_rows(g)
+
     # --- algorithms ---
     def pagerank(self, ctx, g, n_vertices, max_iterations=100, damping=0.85, eps=1e-5):
         out = np.zeros(n_vertices, dtype=np.float64)
@@ -196,6 +202,10 @@ class Native:
     def pagerank_iterate(self, run, n):
         self._check(self.lib.mgx_pagerank_iterate(run, ctypes.c_int64(n)),
                     "mgx_pagerank_iterate")
+
+    def pagerank_xcd_lds_floats(self, run):
+        """Floats per block of the striped launch's LDS hot prefix (0 = none)."""
+        return self.lib.mgx_pagerank_xcd_lds_floats(run)
 
     def pagerank_timing(self, run):
         ms = ctypes.c_double()
