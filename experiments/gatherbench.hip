@@ -14,9 +14,15 @@
 // whose address is the LDS or the global one, and both loads unconditional
 // with a select (LDS lanes re-read table[0]).
 //
+// The mode takes the block width and the resident blocks per CU as well: the
+// same waves per CU in fewer, wider blocks share a larger table
+// (profiles/lds_wide_blocks.md). It prints f = 0 (what the geometry alone
+// costs) and the given share.
+//
 // Build: hipcc --offload-arch=gfx950 -O3 gatherbench.hip -o gatherbench
 // Run:   ./gatherbench [table_mb...]
 //        ./gatherbench lds [K floats, default 5632]
+//        ./gatherbench lds K <256|512|768|896|1024> <blocks per CU> <f>
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -82,12 +88,12 @@ __device__ inline float lds_or_table(const float *lds, const float *table, uint3
   }
 }
 
-template <int FORM>
-__global__ void __launch_bounds__(kBlock) k_gather_lds(int64_t n, const int32_t *idx,
-                                                       const float *table, uint32_t k,
-                                                       double *out) {
+template <int FORM, int THREADS>
+__global__ void __launch_bounds__(THREADS) k_gather_lds(int64_t n, const int32_t *idx,
+                                                        const float *table, uint32_t k,
+                                                        double *out) {
   extern __shared__ float hot_lds[];
-  for (uint32_t i = threadIdx.x; i < k; i += kBlock) hot_lds[i] = table[i];
+  for (uint32_t i = threadIdx.x; i < k; i += THREADS) hot_lds[i] = table[i];
   __syncthreads();
   typedef int v4i __attribute__((ext_vector_type(4)));
   const v4i *idx4 = reinterpret_cast<const v4i *>(idx);
@@ -115,27 +121,35 @@ __global__ void __launch_bounds__(kBlock) k_gather_lds(int64_t n, const int32_t 
     acc += (double)g6;
     acc += (double)g7;
   }
-  __shared__ double red[kBlock / 64];
+  __shared__ double red[THREADS / 64];
   for (int o = 32; o; o >>= 1) acc += __shfl_down(acc, o, 64);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(out, red[0] + red[1] + red[2] + red[3]);
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int i = 0; i < THREADS / 64; ++i) s += red[i];
+    atomicAdd(out, s);
+  }
 }
 
-template <int FORM>
+template <int FORM, int THREADS>
 double run_lds(int64_t n_idx, const int32_t *d_idx, const float *d_table, uint32_t k,
                double *d_out, int grid) {
   hipEvent_t e0, e1;
   TRY(hipEventCreate(&e0));
   TRY(hipEventCreate(&e1));
   const size_t lds = (size_t)(k ? k : 1) * 4;
-  hipLaunchKernelGGL((k_gather_lds<FORM>), dim3(grid), dim3(kBlock), lds, 0, n_idx, d_idx,
-                     d_table, k, d_out);
+  // Past the default per-block limit the kernel has to be told.
+  TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_gather_lds<FORM, THREADS>),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((k_gather_lds<FORM, THREADS>), dim3(grid), dim3(THREADS), lds, 0, n_idx,
+                     d_idx, d_table, k, d_out);
+  TRY(hipGetLastError());
   TRY(hipDeviceSynchronize());
   TRY(hipEventRecord(e0));
   for (int r = 0; r < 5; ++r)
-    hipLaunchKernelGGL((k_gather_lds<FORM>), dim3(grid), dim3(kBlock), lds, 0, n_idx, d_idx,
-                       d_table, k, d_out);
+    hipLaunchKernelGGL((k_gather_lds<FORM, THREADS>), dim3(grid), dim3(THREADS), lds, 0, n_idx,
+                       d_idx, d_table, k, d_out);
   TRY(hipEventRecord(e1));
   TRY(hipEventSynchronize(e1));
   float ms = 0;
@@ -145,10 +159,12 @@ double run_lds(int64_t n_idx, const int32_t *d_idx, const float *d_table, uint32
   return ms / 5.0;
 }
 
-// f in {0, 0.25, 0.4} of the gathers served from a k-float LDS prefix, the
-// rest from a 4 MB (L2-resident) table; unroll 8, resident grid of 7 blocks
-// per CU as in the striped sweep.
-int lds_mode(uint32_t k) {
+// A share f of the gathers served from a k-float LDS prefix, the rest from a
+// 4 MB (L2-resident) table; unroll 8, a grid of per_cu blocks of THREADS per
+// CU, which the occupancy query must confirm resident. share < 0: the f
+// series {0, 0.25, 0.4} of profiles/lds_hot_prefix.md.
+template <int THREADS>
+int lds_mode(uint32_t k, int per_cu, double share) {
   const int64_t n_idx = 1ll << 30;
   const uint32_t mask = (4u << 20) / 4 - 1;
   int32_t *d_idx = nullptr;
@@ -158,20 +174,29 @@ int lds_mode(uint32_t k) {
   TRY(hipMalloc(&d_out, 8));
   TRY(hipMalloc(&d_table, (size_t)(mask + 1) * 4));
   TRY(hipMemset(d_table, 0x3f, (size_t)(mask + 1) * 4));
-  int cus = 0;
+  int cus = 0, block_lds = 0, resident = 0;
   TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0));
-  const int grid = 7 * cus;
-  printf("lds mode: K=%u floats, 4 MB table, unroll 8, grid %d\n", k, grid);
+  TRY(hipDeviceGetAttribute(&block_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, 0));
+  TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_gather_lds<1, THREADS>),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)(k ? k : 1) * 4));
+  TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, k_gather_lds<1, THREADS>, THREADS,
+                                                   (size_t)(k ? k : 1) * 4));
+  const int grid = per_cu * cus;
+  printf("lds mode: K=%u floats, %d threads x %d blocks per CU (occupancy query: %d; "
+         "per-block LDS attribute %d B), 4 MB table, unroll 8, grid %d\n",
+         k, THREADS, per_cu, resident, block_lds, grid);
   printf("%6s %10s %10s %12s\n", "f", "form", "ms", "Ggather/s");
   const char *names[3] = {"table", "flat", "select"};
-  for (double f : {0.0, 0.25, 0.4}) {
+  std::vector<double> fs = {0.0, 0.25, 0.4};
+  if (share >= 0.0) fs = {0.0, share};
+  for (double f : fs) {
     const uint32_t hot = (uint32_t)(f * 4294967296.0);
     hipLaunchKernelGGL(k_fill_idx_hot, dim3(4096), dim3(kBlock), 0, 0, n_idx, mask, k, hot,
                        1ull, d_idx);
     TRY(hipDeviceSynchronize());
-    const double ms[3] = {run_lds<0>(n_idx, d_idx, d_table, k, d_out, grid),
-                          run_lds<1>(n_idx, d_idx, d_table, k, d_out, grid),
-                          run_lds<2>(n_idx, d_idx, d_table, k, d_out, grid)};
+    const double ms[3] = {run_lds<0, THREADS>(n_idx, d_idx, d_table, k, d_out, grid),
+                          run_lds<1, THREADS>(n_idx, d_idx, d_table, k, d_out, grid),
+                          run_lds<2, THREADS>(n_idx, d_idx, d_table, k, d_out, grid)};
     for (int m = 0; m < 3; ++m)
       printf("%6.2f %10s %10.3f %12.2f\n", f, names[m], ms[m], (double)n_idx / (ms[m] * 1e6));
     fflush(stdout);
@@ -180,6 +205,17 @@ int lds_mode(uint32_t k) {
   TRY(hipFree(d_idx));
   TRY(hipFree(d_out));
   return 0;
+}
+
+int lds_mode_for(int threads, uint32_t k, int per_cu, double share) {
+  switch (threads) {
+    case 256: return lds_mode<256>(k, per_cu, share);
+    case 512: return lds_mode<512>(k, per_cu, share);
+    case 768: return lds_mode<768>(k, per_cu, share);
+    case 896: return lds_mode<896>(k, per_cu, share);
+    case 1024: return lds_mode<1024>(k, per_cu, share);
+    default: fprintf(stderr, "block width %d is not built\n", threads); return 2;
+  }
 }
 
 // The sweep's wide-row shape: int4 nontemporal index loads + G independent
@@ -243,7 +279,8 @@ double run_one(int64_t n_idx, const int32_t *d_idx, const float *d_table, double
 
 int main(int argc, char **argv) {
   if (argc > 1 && std::string(argv[1]) == "lds")
-    return lds_mode(argc > 2 ? (uint32_t)atol(argv[2]) : 5632u);
+    return lds_mode_for(argc > 3 ? atoi(argv[3]) : 256, argc > 2 ? (uint32_t)atol(argv[2]) : 5632u,
+                        argc > 4 ? atoi(argv[4]) : 7, argc > 5 ? atof(argv[5]) : -1.0);
   const int64_t n_idx = 1ll << 30;  // 1Gi gathers per pass (the RMAT-26 edge count)
   int32_t *d_idx = nullptr;
   double *d_out = nullptr;

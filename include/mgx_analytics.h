@@ -146,6 +146,9 @@ mgx_status mgx_pagerank_iterate_eps(mgx_pagerank_run *run, int64_t max_n,
 /* Floats of each XCD stripe's hot prefix that this run's striped launch keeps
  * in LDS per block (MGX_PR_XCD_LDS, or the automatic size); 0 = no table. */
 int64_t mgx_pagerank_xcd_lds_floats(const mgx_pagerank_run *run);
+/* Threads per block of this run's striped launch (MGX_PR_XCD_BLOCK, or the
+ * default width); 0 when the run has no striped launch. */
+int mgx_pagerank_xcd_block_threads(const mgx_pagerank_run *run);
 /* Sweep timing accumulated so far (ms) and launch count. */
 mgx_status mgx_pagerank_timing(mgx_pagerank_run *run, double *sweep_ms, int64_t *launches);
 mgx_status mgx_pagerank_finish(mgx_pagerank_run *run, double *out_rank /* nullable */);

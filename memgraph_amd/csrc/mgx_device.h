@@ -76,21 +76,29 @@ __device__ inline void for_bin_section(const int64_t (&goff)[4], F &&f) {
   for_bin_section(goff, (int64_t)blockIdx.x, static_cast<F &&>(f));
 }
 
-// Grid-stride over the rows of section `sec`, kBlock/LANES rows per block per
-// step. Every thread of the block takes every step: step(rowp, live, sub),
-// where *rowp is this thread's row if live (the groups past the end of the
-// last step are not) and sub its lane within the LANES sharing the row.
-template <int LANES, typename Step>
-__device__ inline void for_bin_row_steps(const mgx_bin_sections &S, int sec,
-                                         int64_t block_in_sec, Step &&step) {
-  constexpr int RPB = kBlock / LANES;
-  const int64_t nrows = S.n[sec];
-  const int32_t *rows_list = S.rows + S.off[sec];
+// Grid-stride over the rows of section `sec`, THREADS/LANES rows per block per
+// step, for block `block` of `nblocks`. Every thread of the block takes every
+// step: step(rowp, live, sub), where *rowp is this thread's row if live (the
+// groups past the end of the last step are not) and sub its lane within the
+// LANES sharing the row.
+template <int LANES, int THREADS = kBlock, typename Step>
+__device__ inline void for_row_steps(const int32_t *rows_list, int64_t nrows, int64_t block,
+                                     int64_t nblocks, Step &&step) {
+  static_assert(THREADS % LANES == 0, "whole rows per block");
+  constexpr int RPB = THREADS / LANES;
   const int sub = threadIdx.x % LANES;
-  for (int64_t base = block_in_sec * RPB; base < nrows; base += S.grid[sec] * RPB) {
+  for (int64_t base = block * RPB; base < nrows; base += nblocks * RPB) {
     const int64_t ri = base + threadIdx.x / LANES;
     step(rows_list + ri, ri < nrows, sub);
   }
+}
+
+// The same over section `sec` as block `block_in_sec` of the section's grid.
+template <int LANES, int THREADS = kBlock, typename Step>
+__device__ inline void for_bin_row_steps(const mgx_bin_sections &S, int sec,
+                                         int64_t block_in_sec, Step &&step) {
+  for_row_steps<LANES, THREADS>(S.rows + S.off[sec], S.n[sec], block_in_sec, S.grid[sec],
+                                static_cast<Step &&>(step));
 }
 
 // f(row, sub) for every row of the section, by each of the row's LANES lanes.
@@ -104,41 +112,61 @@ __device__ inline void for_bin_rows(const mgx_bin_sections &S, int sec, int64_t 
 
 // Reduce v over the LANES lanes of a row; the result is valid in the row's
 // lane 0. Sub-wave rows: shuffle tree of width LANES. 256 lanes: wave tree,
-// one LDS slot per wave, thread 0 combines the slots left to right. The
-// 256-lane caller must __syncthreads() before its next row_reduce (the slots
-// are reused).
-template <int LANES, typename T, typename Op>
+// one LDS slot per wave, the row's thread 0 combines its four slots left to
+// right; a block of THREADS > 256 is THREADS / 256 such teams of four waves,
+// each with its own slots. The 256-lane caller must __syncthreads() before
+// its next row_reduce (the slots are reused).
+template <int LANES, int THREADS = kBlock, typename T, typename Op>
 __device__ inline T row_reduce(T v, Op op) {
   if constexpr (LANES <= 64) {
     for (int o = LANES / 2; o; o >>= 1) v = op(v, __shfl_down(v, o, LANES));
   } else {
-    __shared__ T red[kBlock / 64];
+    static_assert(LANES == 256, "a row takes a sub-wave group or four waves");
+    __shared__ T red[THREADS / 64];
     for (int o = 32; o; o >>= 1) v = op(v, __shfl_down(v, o, 64));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
-    if (threadIdx.x == 0) v = op(op(op(red[0], red[1]), red[2]), red[3]);
+    if constexpr (THREADS == LANES) {
+      if (threadIdx.x == 0) v = op(op(op(red[0], red[1]), red[2]), red[3]);
+    } else {
+      const int w = threadIdx.x >> 6;  // this team's first slot, in its thread 0
+      if (threadIdx.x % LANES == 0) v = op(op(op(red[w], red[w + 1]), red[w + 2]), red[w + 3]);
+    }
   }
   return v;
 }
 
-// The gather-reduce-write sweep over a section: each lane of a row computes
+// The gather-reduce-write sweep over a row list: each lane of a row computes
 // gather(row, sub), the row's lanes are combined with op (idle groups
 // contribute `identity`), and the row's lane 0 calls finish(row, value).
-template <int LANES, typename T, typename Op, typename Gather, typename Finish>
+template <int LANES, int THREADS = kBlock, typename T, typename Op, typename Gather,
+          typename Finish>
+__device__ inline void reduce_rows(const int32_t *rows_list, int64_t nrows, int64_t block,
+                                   int64_t nblocks, T identity, Op op, Gather &&gather,
+                                   Finish &&finish) {
+  for_row_steps<LANES, THREADS>(
+      rows_list, nrows, block, nblocks, [&](const int32_t *rowp, bool live, int sub) {
+        T v = identity;
+        int32_t row = -1;
+        if (live) {
+          row = *rowp;
+          v = gather(row, sub);
+        }
+        v = row_reduce<LANES, THREADS>(v, op);
+        if (sub == 0 && row >= 0) finish(row, v);
+        if constexpr (LANES > 64) __syncthreads();  // row_reduce's slots are reused
+      });
+}
+
+// The same over section `sec` as block `block_in_sec` of the section's grid.
+template <int LANES, int THREADS = kBlock, typename T, typename Op, typename Gather,
+          typename Finish>
 __device__ inline void reduce_bin_rows(const mgx_bin_sections &S, int sec,
                                        int64_t block_in_sec, T identity, Op op,
                                        Gather &&gather, Finish &&finish) {
-  for_bin_row_steps<LANES>(S, sec, block_in_sec, [&](const int32_t *rowp, bool live, int sub) {
-    T v = identity;
-    int32_t row = -1;
-    if (live) {
-      row = *rowp;
-      v = gather(row, sub);
-    }
-    v = row_reduce<LANES>(v, op);
-    if (sub == 0 && row >= 0) finish(row, v);
-    if constexpr (LANES > 64) __syncthreads();  // row_reduce's slots are reused
-  });
+  reduce_rows<LANES, THREADS>(S.rows + S.off[sec], S.n[sec], block_in_sec, S.grid[sec],
+                              identity, op, static_cast<Gather &&>(gather),
+                              static_cast<Finish &&>(finish));
 }
 
 // f(c) for every column of CSR range [s, e) owned by lane `sub` of LANES.
@@ -166,18 +194,19 @@ __device__ inline void row_gather(const int32_t *col, uint32_t s, uint32_t e, in
   }
 }
 
-// Reduce v over a kBlock-thread block (wave tree, one LDS slot per wave,
+// Reduce v over a THREADS-thread block (wave tree, one LDS slot per wave,
 // thread 0 folds identity, slot 0, 1, ... left to right) and hand the block's
 // value to atomic(), once per block.
-template <typename T, typename Op, typename Atomic>
+template <int THREADS = kBlock, typename T, typename Op, typename Atomic>
 __device__ inline void block_reduce_atomic(T v, T identity, Op op, Atomic atomic) {
-  __shared__ T red[kBlock / 64];
+  static_assert(THREADS % 64 == 0, "whole waves");
+  __shared__ T red[THREADS / 64];
   for (int o = 32; o; o >>= 1) v = op(v, __shfl_down(v, o, 64));
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
   if (threadIdx.x == 0) {
     T s = identity;
-    for (int i = 0; i < kBlock / 64; ++i) s = op(s, red[i]);
+    for (int i = 0; i < THREADS / 64; ++i) s = op(s, red[i]);
     atomic(s);
   }
 }

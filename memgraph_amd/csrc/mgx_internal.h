@@ -262,6 +262,9 @@ struct mgx_pagerank_run {
   // (stripe-major) for the XCD-striped one.
   double *d_partial = nullptr;
   int xcd_grid = 0;  // XCD-striped launch: resident grid, a multiple of 8
+  // XCD-striped launch: threads per block, chosen when the run starts
+  // (MGX_PR_XCD_BLOCK); 0 when the run has no striped launch.
+  int xcd_block = 0;
   // XCD-striped launch: floats of each stripe's hot prefix held in LDS per
   // block (0 = none), chosen when the run starts (MGX_PR_XCD_LDS).
   int64_t xcd_lds_floats = 0;

@@ -189,15 +189,18 @@ __global__ void __launch_bounds__(kBlock) k_pr_sweep(PrArgs A) {
 }
 
 // XCD-striped sweep over the heavy rows (mgx_graph::xcd). Block b gathers
-// only from source stripe b & 7 and acts as block b >> 3 of that stripe's
-// bin sections (rows are slots here), so the blocks that share an XCD — b
-// and b + 8 under the observed round-robin dispatch — share one eighth of
-// contrib and the eight L2s hold eight different slices. The grid is
-// resident at once and strides over the stripe's section blocks, so that
-// placement does not depend on redispatch order. Each segment's fp64 sum
-// goes to partial[x * nH + slot]; k_pr_finish_heavy combines them. No
-// block reads what another wrote: a different placement changes the speed
-// only.
+// only from source stripe b & 7 and acts as block b >> 3 of that stripe
+// (rows are slots here), so the blocks that share an XCD — b and b + 8 under
+// the observed round-robin dispatch — share one eighth of contrib and the
+// eight L2s hold eight different slices. The grid is resident at once and
+// each block strides over the rows of the stripe's four bin sections in turn,
+// the 256-lane section (the longest segments) first, so that placement does
+// not depend on redispatch order. A block of THREADS threads takes
+// THREADS / LANES segments per step; a segment's lanes, their share of the
+// columns and the order of its additions are those of a 256-thread block, so
+// every width gives the same bits. Each segment's fp64 sum goes to
+// partial[x * nH + slot]; k_pr_finish_heavy combines them. No block reads
+// what another wrote: a different placement changes the speed only.
 struct PrXcdArgs {
   const int32_t *col;
   const float *contrib_old;
@@ -214,10 +217,10 @@ struct PrXcdArgs {
 // The stripe is hot-first inside, so that prefix takes the largest share of
 // the gathers a table of this size can; contrib_old is read-only for the
 // whole launch. Every gathered value has the same bits either way.
-// The two 64-bit flat addresses per gather would take HOT to 78 VGPRs and 6
-// waves per SIMD; it is held to the 7-wave step the plain launch has (70).
-template <bool HOT>
-__global__ void __launch_bounds__(kBlock, HOT ? 7 : 1) k_pr_sweep_xcd(PrXcdArgs X) {
+// With one section's loop live at a time every instantiation stays below 64
+// VGPRs (8 waves per SIMD) without a bound on the registers.
+template <bool HOT, int THREADS>
+__global__ void __launch_bounds__(THREADS) k_pr_sweep_xcd(PrXcdArgs X) {
   const int x = blockIdx.x % kXcdStripes;
   const mgx_bin_sections &S = X.sec[x];
   PrArgs A;  // only what pr_row_sum reads
@@ -225,29 +228,49 @@ __global__ void __launch_bounds__(kBlock, HOT ? 7 : 1) k_pr_sweep_xcd(PrXcdArgs 
   A.sp_lo = X.xptr + (size_t)x * X.nH;
   A.sp_hi = A.sp_lo + X.nH;
   double *out = X.partial + (size_t)x * X.nH;
-  const int64_t vgrid = S.goff[3] + S.grid[3];
-  const int64_t stride = gridDim.x / kXcdStripes;
+  const int64_t block = blockIdx.x / kXcdStripes;
+  const int64_t nblocks = gridDim.x / kXcdStripes;
   auto sweep = [&](auto load) {
-    for (int64_t vb = blockIdx.x / kXcdStripes; vb < vgrid; vb += stride) {
-      for_bin_section(S.goff, vb, [&](auto lanes, int sec, int64_t bis) {
-        constexpr int L = decltype(lanes)::value;
-        reduce_bin_rows<L>(
-            S, sec, bis, 0.0, mgx_op_add(),
-            [&](int32_t slot, int sub) { return pr_row_sum<L>(A, slot, sub, load); },
-            [&](int32_t slot, double acc) { out[slot] = acc; });
-      });
-    }
+    // Every thread takes every step of the 256-lane section (reduce_rows
+    // counts them per block, not per team), so its barriers are block-wide.
+    auto section = [&](auto lanes, int sec) {
+      constexpr int L = decltype(lanes)::value;
+      reduce_rows<L, THREADS>(
+          S.rows + S.off[sec], S.n[sec], block, nblocks, 0.0, mgx_op_add(),
+          [&](int32_t slot, int sub) { return pr_row_sum<L>(A, slot, sub, load); },
+          [&](int32_t slot, double acc) { out[slot] = acc; });
+    };
+    section(std::integral_constant<int, 256>{}, 3);
+    section(std::integral_constant<int, 64>{}, 2);
+    section(std::integral_constant<int, 16>{}, 1);
+    section(std::integral_constant<int, 4>{}, 0);
   };
   if constexpr (HOT) {
     extern __shared__ float hot[];
     const int64_t base = mgx_xcd_stripe_off(X.V, x);
     const int64_t len = mgx_xcd_stripe_off(X.V, x + 1) - base;
     const uint32_t kx = len < (int64_t)X.hot_k ? (uint32_t)len : X.hot_k;
-    for (uint32_t i = threadIdx.x; i < kx; i += kBlock) hot[i] = X.contrib_old[base + i];
+    for (uint32_t i = threadIdx.x; i < kx; i += THREADS) hot[i] = X.contrib_old[base + i];
     __syncthreads();
     sweep(PrLoadHot{X.contrib_old, hot, (uint32_t)base, kx});
   } else {
     sweep(PrLoadGlobal{X.contrib_old});
+  }
+}
+
+// The instantiation for a block width (MGX_PR_XCD_BLOCK), nullptr for a width
+// that is not built. Two blocks of 1024 threads fill a CU's 32 wave slots and
+// share its LDS in halves, a table four times that of eight 256-thread blocks;
+// 512, 768 and 896 threads measured between the two
+// (profiles/lds_wide_blocks.md) and are not built.
+using pr_xcd_kernel = void (*)(PrXcdArgs);
+constexpr int kXcdDefaultWidth = 1024;
+
+pr_xcd_kernel pr_xcd_kernel_for(bool hot, int threads) {
+  switch (threads) {
+    case 256: return hot ? k_pr_sweep_xcd<true, 256> : k_pr_sweep_xcd<false, 256>;
+    case 1024: return hot ? k_pr_sweep_xcd<true, 1024> : k_pr_sweep_xcd<false, 1024>;
+    default: return nullptr;
   }
 }
 
@@ -333,13 +356,9 @@ mgx_status queue_xcd_sweep(mgx_pagerank_run *run, PrArgs A) {
     X.nH = nH;
     X.V = g->n_vertices;
     X.hot_k = (uint32_t)run->xcd_lds_floats;
-    if (X.hot_k > 0) {
-      hipLaunchKernelGGL(k_pr_sweep_xcd<true>, dim3((uint32_t)run->xcd_grid), dim3(kBlock),
-                         (size_t)X.hot_k * sizeof(float), ctx->stream, X);
-    } else {
-      hipLaunchKernelGGL(k_pr_sweep_xcd<false>, dim3((uint32_t)run->xcd_grid), dim3(kBlock), 0,
-                         ctx->stream, X);
-    }
+    hipLaunchKernelGGL(pr_xcd_kernel_for(X.hot_k > 0, run->xcd_block),
+                       dim3((uint32_t)run->xcd_grid), dim3((uint32_t)run->xcd_block),
+                       (size_t)X.hot_k * sizeof(float), ctx->stream, X);
   }
   mgx_bins light = g->bins_in;
   for (int b = g->xcd_heavy_sec; b < 4; ++b) light.count[b] = light.grid[b] = 0;
@@ -508,38 +527,57 @@ mgx_status mgx_pagerank_normalize_download(mgx_pagerank_run *run, double *out_ra
 
 namespace {
 
-// Resident blocks per CU of the striped launch with `floats` of dynamic LDS.
-mgx_status xcd_blocks_per_cu(int64_t floats, int *per_cu) {
-  if (floats > 0) {
-    MGX_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        per_cu, k_pr_sweep_xcd<true>, kBlock, (size_t)floats * sizeof(float)));
-  } else {
-    MGX_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k_pr_sweep_xcd<false>,
-                                                             kBlock, 0));
+// Resident blocks per CU of the striped launch of `threads` per block with
+// `floats` of dynamic LDS.
+mgx_status xcd_blocks_per_cu(int threads, int64_t floats, int *per_cu) {
+  MGX_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+      per_cu, pr_xcd_kernel_for(floats > 0, threads), threads, (size_t)floats * sizeof(float)));
+  return MGX_OK;
+}
+
+// Block width of the striped launch, chosen per run: MGX_PR_XCD_BLOCK=<threads>
+// forces it; a width without a kernel is an error.
+mgx_status pick_xcd_block(int *threads) {
+  *threads = kXcdDefaultWidth;
+  const char *e = getenv("MGX_PR_XCD_BLOCK");
+  if (e && *e) *threads = atoi(e);
+  if (!pr_xcd_kernel_for(false, *threads)) {
+    mgx_set_error("MGX_PR_XCD_BLOCK=%s: the striped sweep has no kernel of that width",
+                  e ? e : "");
+    return MGX_ERR_INVALID_ARGUMENT;
   }
   return MGX_OK;
 }
 
 // Floats of each stripe's hot prefix that the striped launch keeps in LDS
-// (run->xcd_lds_floats), chosen per run. MGX_PR_XCD_LDS=<floats> forces it
-// (0 = the launch without a table), clamped to the longest stripe and to what
-// one block may allocate. Unset: the largest multiple of 256 floats that
-// leaves the occupancy query's blocks per CU where they are with no dynamic
-// LDS; a larger table trades resident waves for LDS hits, which measured
-// slower (profiles/lds_hot_prefix.md).
+// (run->xcd_lds_floats), chosen per run once the width is. MGX_PR_XCD_LDS=
+// <floats> forces it (0 = the launch without a table), clamped to the longest
+// stripe and to what one block may allocate. Unset: the largest multiple of
+// 256 floats that leaves the occupancy query's blocks per CU where they are
+// with no dynamic LDS, 8 blocks of 256 threads or 2 of 1024; a larger table
+// trades resident waves for LDS hits, which measured slower
+// (profiles/lds_hot_prefix.md, profiles/lds_wide_blocks.md).
 mgx_status pick_xcd_lds(mgx_pagerank_run *run) {
   const int64_t V = run->g->n_vertices;
+  const int threads = run->xcd_block;
   int64_t longest = 0;
   for (int x = 0; x < kXcdStripes; ++x) {
     const int64_t len = mgx_xcd_stripe_off(V, x + 1) - mgx_xcd_stripe_off(V, x);
     if (len > longest) longest = len;
   }
+  const void *hot_fn = reinterpret_cast<const void *>(pr_xcd_kernel_for(true, threads));
   hipFuncAttributes fa;
-  MGX_HIP_TRY(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k_pr_sweep_xcd<true>)));
+  MGX_HIP_TRY(hipFuncGetAttributes(&fa, hot_fn));
   int block_lds = 0;
   MGX_HIP_TRY(hipDeviceGetAttribute(&block_lds, hipDeviceAttributeMaxSharedMemoryPerBlock,
                                     run->ctx->device));
   const int64_t most = ((int64_t)block_lds - (int64_t)fa.sharedSizeBytes) / (int64_t)sizeof(float);
+  if (most > 0) {
+    // A table of more than 64 KiB is within the device's limit (one block may
+    // hold a CU's whole LDS), but the kernel has to be told.
+    MGX_HIP_TRY(hipFuncSetAttribute(hot_fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)(most * (int64_t)sizeof(float))));
+  }
   int64_t k = 0;
   const char *e = getenv("MGX_PR_XCD_LDS");
   if (e && *e) {
@@ -547,14 +585,14 @@ mgx_status pick_xcd_lds(mgx_pagerank_run *run) {
     if (k < 0) k = 0;
   } else {
     constexpr int64_t kStep = 256;
-    int base_blocks = 0;
-    MGX_TRY(xcd_blocks_per_cu(0, &base_blocks));
+    int want_blocks = 0;
+    MGX_TRY(xcd_blocks_per_cu(threads, 0, &want_blocks));
     int64_t lo = 0, hi = most / kStep;  // steps: lo keeps the occupancy, above hi does not fit
     while (lo < hi) {
       const int64_t mid = (lo + hi + 1) / 2;
       int blocks = 0;
-      MGX_TRY(xcd_blocks_per_cu(mid * kStep, &blocks));
-      if (blocks >= base_blocks) lo = mid;
+      MGX_TRY(xcd_blocks_per_cu(threads, mid * kStep, &blocks));
+      if (blocks >= want_blocks) lo = mid;
       else hi = mid - 1;
     }
     k = lo * kStep;
@@ -573,10 +611,14 @@ mgx_status pagerank_start_common(mgx_context *ctx, mgx_graph *g, double damping,
     mgx_set_error("pagerank needs a graph built with MGX_BUILD_IN_CSR");
     return MGX_ERR_INVALID_ARGUMENT;
   }
+  const bool striped = g->xcd && g->xcd_nH > 0;
+  int xcd_block = 0;
+  if (striped) MGX_TRY(pick_xcd_block(&xcd_block));  // before anything is allocated
   auto *run = new mgx_pagerank_run();
   run->ctx = ctx;
   run->g = g;
   run->damping = damping;
+  run->xcd_block = xcd_block;
   run->dist = dist;
   run->row_begin = row_begin;
   run->row_end = row_end;
@@ -595,19 +637,24 @@ mgx_status pagerank_start_common(mgx_context *ctx, mgx_graph *g, double damping,
     const int64_t rows = (dist ? (row_end < V ? row_end : V) : V) - row_begin;
     MGX_TRY(ctx->alloc_async((void **)&run->d_partial, rows * sizeof(double)));
   }
-  if (g->xcd && g->xcd_nH > 0) {
+  if (striped) {
     MGX_TRY(ctx->alloc_async((void **)&run->d_partial,
                              (size_t)kXcdStripes * g->xcd_nH * sizeof(double)));
     MGX_TRY(pick_xcd_lds(run));
     // A grid that is resident at once (occupancy x CUs, a multiple of 8), no
-    // larger than the busiest stripe's sections need.
+    // larger than the busiest section of the busiest stripe can use: a block
+    // takes xcd_block / lanes rows of a section per step.
     int per_cu = 0, cus = 0;
-    MGX_TRY(xcd_blocks_per_cu(run->xcd_lds_floats, &per_cu));
+    MGX_TRY(xcd_blocks_per_cu(run->xcd_block, run->xcd_lds_floats, &per_cu));
     MGX_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
     int64_t want = 0;
     for (int x = 0; x < kXcdStripes; ++x) {
-      const int64_t vg = g->xcd_bins[x].total_grid();
-      if (vg > want) want = vg;
+      const int lanes[4] = {4, 16, 64, 256};
+      for (int b = 0; b < 4; ++b) {
+        const int64_t rows_per_block = run->xcd_block / lanes[b];
+        const int64_t need = (g->xcd_bins[x].count[b] + rows_per_block - 1) / rows_per_block;
+        if (need > want) want = need;
+      }
     }
     int64_t per_stripe = (int64_t)per_cu * cus / kXcdStripes;
     if (per_stripe > want) per_stripe = want;
@@ -676,6 +723,10 @@ extern "C" mgx_status mgx_pagerank_iterate_eps(mgx_pagerank_run *run, int64_t ma
 
 extern "C" int64_t mgx_pagerank_xcd_lds_floats(const mgx_pagerank_run *run) {
   return run->xcd_lds_floats;
+}
+
+extern "C" int mgx_pagerank_xcd_block_threads(const mgx_pagerank_run *run) {
+  return run->xcd_block;
 }
 
 extern "C" mgx_status mgx_pagerank_timing(mgx_pagerank_run *run, double *sweep_ms,

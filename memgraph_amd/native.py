@@ -207,6 +207,10 @@ class Native:
         """Floats per block of the striped launch's LDS hot prefix (0 = none)."""
         return self.lib.mgx_pagerank_xcd_lds_floats(run)
 
+    def pagerank_xcd_block_threads(self, run):
+        """Threads per block of the striped launch (0 = no striped launch)."""
+        return self.lib.mgx_pagerank_xcd_block_threads(run)
+
     def pagerank_timing(self, run):
         ms = ctypes.c_double()
         n = ctypes.c_int64()
