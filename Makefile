@@ -14,10 +14,11 @@ MGX_HIP_SRCS := memgraph_amd/csrc/graph_build.hip memgraph_amd/csrc/pagerank.hip
                 memgraph_amd/csrc/labelrankt.hip memgraph_amd/csrc/leiden.hip \
                 memgraph_amd/csrc/wcc.hip memgraph_amd/csrc/katz.hip \
                 memgraph_amd/csrc/betweenness.hip memgraph_amd/csrc/bfs.hip \
-                memgraph_amd/csrc/louvain.hip memgraph_amd/csrc/similarity.hip
+                memgraph_amd/csrc/louvain.hip memgraph_amd/csrc/similarity.hip \
+                memgraph_amd/csrc/bridges.hip
 MGX_OBJS := $(MGX_SRCS:%.cpp=build/%.o) $(MGX_HIP_SRCS:%.hip=build/%.o)
 
-MODULES := pagerank katz_centrality community_detection weakly_connected_components betweenness_centrality pagerank_online katz_centrality_online community_detection_online leiden_community_detection node_similarity
+MODULES := pagerank katz_centrality community_detection weakly_connected_components betweenness_centrality pagerank_online katz_centrality_online community_detection_online leiden_community_detection node_similarity bridges
 
 all: $(LIBDIR)/libmgx_analytics.so modules mock oracle
 

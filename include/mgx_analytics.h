@@ -1,8 +1,8 @@
 // ============================================================================
 // mgx_analytics — MI355X-native (gfx950/CDNA4) graph-analytics compute
-// library: the GPU back end behind the drop-in MAGE module .so's
-// (pagerank.so, katz_centrality.so, community_detection.so,
-// weakly_connected_components.so).
+// library: the GPU back end behind the eleven drop-in MAGE module .so's
+// (memgraph_amd/modules/: pagerank.so, katz_centrality.so,
+// community_detection.so, weakly_connected_components.so, bridges.so, ...).
 //
 // C ABI: plain pointers and sizes only. Each entry point cites the
 // reference interface it replaces (paths under /root/reference).
@@ -189,6 +189,38 @@ mgx_status mgx_bfs(mgx_context *ctx, mgx_graph *g, int64_t source, int directed,
                    int64_t max_depth /* <0 = unlimited */, int mode,
                    int64_t *out_hops /* nullable */, int64_t *out_parent /* nullable */,
                    mgx_bfs_stats *stats /* nullable */);
+
+/* ---- Bridges (replaces bridges_alg::GetBridges,
+ *      src/mage/cpp/bridges_module/algorithm/bridges.cpp:31-69) ------------
+ * The bridges of the undirected multigraph: an edge is a bridge iff removing
+ * that one edge disconnects its component. Parallel and antiparallel
+ * duplicates and self-loops are never bridges (the reference's
+ * GetEdgesBetweenNodes(...).size() == 1 filter, bridges.cpp:49).
+ * Tarjan-Vishkin on a BFS forest: WCC min-member roots, one multi-source
+ * direction-optimizing BFS, subtree preorder intervals, low/high by one
+ * degree-binned sweep over the sym-CSR, level-synchronous folds. */
+typedef struct {
+  int64_t bridges, trees, depth;      /* depth = deepest BFS level of the forest */
+  int64_t nontree_entries;            /* sym-CSR entries that are not "the one" parent entry */
+  int64_t level_launches;             /* per-level kernel launches of the three tree passes */
+  double forest_ms, ms;               /* HIP events; ms = whole call minus download */
+} mgx_bridges_stats;
+/* Needs MGX_BUILD_SYM_CSR (weights ignored). Bridges as unordered pairs
+ * out_u[i] < out_v[i], sorted ascending by (u, v); capacity V entries each.
+ * Deterministic. */
+mgx_status mgx_bridges(mgx_context *ctx, mgx_graph *g, int64_t *out_u, int64_t *out_v,
+                       int64_t *n_bridges, mgx_bridges_stats *stats /* nullable */);
+/* Test support: the forest and interval state the call computed, by vertex:
+ * parent (minimum-id neighbour one level up, parent[root] = root), BFS level,
+ * global preorder number, subtree size, and low/high = min/max preorder
+ * number reachable from the subtree by one non-tree entry. All nullable. */
+mgx_status mgx_bridges_state(mgx_context *ctx, mgx_graph *g, int64_t *parent, int64_t *level,
+                             int64_t *pre, int64_t *nd, int64_t *low, int64_t *high);
+/* Measurement support: HIP-event split of this thread's last mgx_bridges call
+ * (ms): forest (WCC + BFS), sorts and scans, the low/high sweep, and the
+ * 3 * depth per-level launches. They sum to stats.ms. All nullable. */
+void mgx_bridges_last_stage_ms(double *forest, double *sorts_scans, double *sweep,
+                               double *levels);
 
 /* ---- Node similarity: Jaccard and overlap of out-neighbour sets (replaces
  *      node_similarity_algs::CalculateSimilarityPairwise / ...Cartesian,

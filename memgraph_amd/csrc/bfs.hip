@@ -36,6 +36,13 @@
 // neighbours against fcur and stops at the first chunk with a hit; the
 // lowest hitting lane is the minimum-id predecessor.
 // Direction: Beamer's rule with the growing/shrinking guard.
+//
+// mgx_bfs_device is the traversal itself, seeded from a device list of roots
+// (level 0) and leaving hops / parent on the device: bridges.hip runs it from
+// every component's minimum member at once. mgx_bfs is the single-source
+// wrapper that widens and downloads. With several roots the queue order
+// within a level depends on atomics, the results do not: hops is the level
+// and parent the atomicMin / lowest-lane minimum, as with one source.
 
 #include <algorithm>
 #include <climits>
@@ -49,7 +56,8 @@ constexpr int64_t kGridCap = 2048;  // element-wise launches of this file
 
 struct BfsCounters {
   uint32_t tail[4];            // cumulative entries queued per degree class
-  uint32_t pad[2];
+  uint32_t seed_zero;          // level-0 vertices of a root list that have no entries
+  uint32_t pad;
   unsigned long long degsum;   // cumulative degree sum of reached vertices
   unsigned long long reached;  // cumulative reached vertices
   unsigned long long scanned;  // cumulative entries examined bottom-up
@@ -100,20 +108,42 @@ __global__ void k_bfs_init(int64_t n, int32_t *hops, int32_t *parent) {
   }
 }
 
-__global__ void k_bfs_seed(int32_t source, const uint32_t *row_ptr, int32_t *hops,
-                           int32_t *parent, uint32_t *visited, uint32_t *fcur, int32_t *q01,
-                           int32_t *q23, int64_t V, BfsCounters *cnt) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  const uint32_t deg = row_ptr[source + 1] - row_ptr[source];
-  const int c = degree_class(deg);
-  hops[source] = 0;
-  if (parent) parent[source] = source;
-  visited[source >> 5] = 1u << (source & 31);
-  fcur[source >> 5] = 1u << (source & 31);
-  *qslot(q01, q23, V, c, 0) = source;
-  cnt->tail[c] = 1;
-  cnt->degsum = deg;
-  cnt->reached = 1;
+// Level 0: the n_roots distinct vertices of `roots` (or the one vertex
+// `single` when roots is null). One thread per root; the grid covers whole
+// waves so the ballot in enqueue() sees converged lanes.
+__global__ void k_bfs_seed(const int32_t *roots, int64_t n_roots, int32_t single,
+                           const uint32_t *row_ptr, int32_t *hops, int32_t *parent,
+                           uint32_t *visited, uint32_t *fcur, int32_t *q01, int32_t *q23,
+                           int64_t V, BfsCounters *cnt) {
+  const int64_t n64 = (n_roots + 63) / 64 * 64;
+  unsigned long long acc_deg = 0, acc_n = 0, acc_zero = 0;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n64;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const bool live = i < n_roots;
+    int32_t r = 0;
+    int cls = 0;
+    if (live) {
+      r = roots ? roots[i] : single;
+      const uint32_t deg = row_ptr[r + 1] - row_ptr[r];
+      cls = degree_class(deg);
+      if (roots && deg == 0u) acc_zero += 1;
+      hops[r] = 0;
+      if (parent) parent[r] = r;
+      atomicOr(&visited[(uint32_t)r >> 5], 1u << (r & 31));
+      atomicOr(&fcur[(uint32_t)r >> 5], 1u << (r & 31));
+      acc_deg += deg;
+      acc_n += 1;
+    }
+    enqueue(live, cls, r, q01, q23, V, cnt);
+  }
+  acc_deg = wave_sum(acc_deg);
+  acc_n = wave_sum(acc_n);
+  acc_zero = wave_sum(acc_zero);
+  if ((threadIdx.x & 63) == 0 && acc_n) {
+    atomicAdd(&cnt->degsum, acc_deg);
+    atomicAdd(&cnt->reached, acc_n);
+    if (acc_zero) atomicAdd(&cnt->seed_zero, (uint32_t)acc_zero);
+  }
 }
 
 // ---- top-down ------------------------------------------------------------
@@ -344,9 +374,9 @@ int64_t env_positive(const char *name, int64_t dflt) {
 
 }  // namespace
 
-mgx_status mgx_bfs_impl(mgx_context *ctx, mgx_graph *g, int64_t source, int directed,
-                        int64_t max_depth, int mode, int64_t *out_hops, int64_t *out_parent,
-                        mgx_bfs_stats *stats) {
+namespace {
+
+mgx_status bfs_check_args(mgx_graph *g, int directed, int mode) {
   if (mode != MGX_BFS_AUTO && mode != MGX_BFS_TOP_DOWN && mode != MGX_BFS_BOTTOM_UP) {
     mgx_set_error("bfs: unknown mode %d", mode);
     return MGX_ERR_INVALID_ARGUMENT;
@@ -361,24 +391,31 @@ mgx_status mgx_bfs_impl(mgx_context *ctx, mgx_graph *g, int64_t source, int dire
                   directed ? "OUT" : "SYM");
     return MGX_ERR_INVALID_ARGUMENT;
   }
+  return MGX_OK;
+}
+
+}  // namespace
+
+// The traversal with its seeds and results on the device: level 0 is the
+// n_roots distinct vertices of d_roots (or the one vertex `single` when
+// d_roots is null); hops [V] and parent [V] (nullable) are the caller's
+// buffers and are left holding -1 / INT32_MAX where nothing was reached.
+// stats->ms covers init to last level.
+mgx_status mgx_bfs_device(mgx_context *ctx, mgx_graph *g, const int32_t *d_roots,
+                          int64_t n_roots, int32_t single, int directed, int64_t max_depth,
+                          int mode, int32_t *hops, int32_t *parent, mgx_bfs_stats *stats) {
+  MGX_TRY(bfs_check_args(g, directed, mode));
   const int64_t V = g->n_vertices;
-  if (source < 0 || source >= V) {
-    mgx_set_error("bfs: source %lld outside [0,%lld)", (long long)source, (long long)V);
-    return MGX_ERR_INVALID_ARGUMENT;
-  }
   const uint32_t *row_ptr = directed ? g->out_row_ptr : g->sym_row_ptr;
   const int32_t *col = directed ? g->out_col : g->sym_col;
   const int64_t total_entries = directed ? g->n_edges : 2 * g->n_edges;
   const int64_t alpha = env_positive("MGX_BFS_ALPHA", 14);
   const int64_t beta = env_positive("MGX_BFS_BETA", 24);
-  const bool want_parent = out_parent != nullptr;
   const int64_t W = (V + 31) / 32;
 
-  int32_t *hops = nullptr, *parent = nullptr, *q01 = nullptr, *q23 = nullptr;
+  int32_t *q01 = nullptr, *q23 = nullptr;
   uint32_t *visited = nullptr, *fcur = nullptr, *fnext = nullptr;
   BfsCounters *d_cnt = nullptr;
-  MGX_TRY(ctx->alloc_async((void **)&hops, V * sizeof(int32_t)));
-  if (want_parent) MGX_TRY(ctx->alloc_async((void **)&parent, V * sizeof(int32_t)));
   MGX_TRY(ctx->alloc_async((void **)&q01, V * sizeof(int32_t)));
   MGX_TRY(ctx->alloc_async((void **)&q23, V * sizeof(int32_t)));
   MGX_TRY(ctx->alloc_async((void **)&visited, W * sizeof(uint32_t)));
@@ -400,8 +437,9 @@ mgx_status mgx_bfs_impl(mgx_context *ctx, mgx_graph *g, int64_t source, int dire
   MGX_HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(BfsCounters), ctx->stream));
   hipLaunchKernelGGL(k_bfs_init, dim3((uint32_t)grid_for(V, kGridCap)), dim3(kBlock), 0,
                      ctx->stream, V, hops, parent);
-  hipLaunchKernelGGL(k_bfs_seed, dim3(1), dim3(64), 0, ctx->stream, (int32_t)source, row_ptr,
-                     hops, parent, visited, fcur, q01, q23, V, d_cnt);
+  hipLaunchKernelGGL(k_bfs_seed, dim3((uint32_t)grid_for(n_roots, kGridCap)), dim3(kBlock), 0,
+                     ctx->stream, d_roots, n_roots, single, row_ptr, hops, parent, visited, fcur,
+                     q01, q23, V, d_cnt);
 
   // One small D2H readback of the counter block per level.
   BfsCounters h;
@@ -413,7 +451,11 @@ mgx_status mgx_bfs_impl(mgx_context *ctx, mgx_graph *g, int64_t source, int dire
   };
   MGX_TRY(read_counters(&h));
 
-  int64_t n_f = 1, prev_n_f = 0;          // frontier size, previous level's
+  // Frontier size, previous level's. Roots of a list that have no entries
+  // (isolated vertices: most of the 7.9 M roots of an RMAT-24 forest) are no
+  // frontier for the growing guard below: counted, they made level 1 look
+  // like a shrinking frontier and kept its 45 ms top-down.
+  int64_t n_f = (int64_t)h.reached - (int64_t)h.seed_zero, prev_n_f = 0;
   int64_t m_f = (int64_t)h.degsum;        // frontier degree sum
   int64_t m_u = total_entries - m_f;      // unvisited degree sum
   uint32_t q_start[4] = {0, 0, 0, 0}, q_end[4];
@@ -532,6 +574,44 @@ mgx_status mgx_bfs_impl(mgx_context *ctx, mgx_graph *g, int64_t source, int dire
   }
 
   MGX_HIP_TRY(hipEventRecord(ev1, ctx->stream));
+  MGX_HIP_TRY(hipEventSynchronize(ev1));
+  float ms = 0.f;
+  MGX_HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+  MGX_HIP_TRY(hipEventDestroy(ev0));
+  MGX_HIP_TRY(hipEventDestroy(ev1));
+  if (stats) {
+    stats->depth = depth;
+    stats->reached = (int64_t)h.reached;
+    stats->entries_scanned = td_scanned + (int64_t)h.scanned;
+    stats->top_down_levels = td_levels;
+    stats->bottom_up_levels = bu_levels;
+    stats->bottom_up_mask = bu_mask;
+    stats->ms = ms;
+  }
+  MGX_TRY(ctx->free_async(q01));
+  MGX_TRY(ctx->free_async(q23));
+  MGX_TRY(ctx->free_async(visited));
+  MGX_TRY(ctx->free_async(fcur));
+  MGX_TRY(ctx->free_async(fnext));
+  MGX_TRY(ctx->free_async(d_cnt));
+  MGX_HIP_TRY(hipGetLastError());
+  return MGX_OK;
+}
+
+mgx_status mgx_bfs_impl(mgx_context *ctx, mgx_graph *g, int64_t source, int directed,
+                        int64_t max_depth, int mode, int64_t *out_hops, int64_t *out_parent,
+                        mgx_bfs_stats *stats) {
+  MGX_TRY(bfs_check_args(g, directed, mode));
+  const int64_t V = g->n_vertices;
+  if (source < 0 || source >= V) {
+    mgx_set_error("bfs: source %lld outside [0,%lld)", (long long)source, (long long)V);
+    return MGX_ERR_INVALID_ARGUMENT;
+  }
+  int32_t *hops = nullptr, *parent = nullptr;
+  MGX_TRY(ctx->alloc_async((void **)&hops, V * sizeof(int32_t)));
+  if (out_parent) MGX_TRY(ctx->alloc_async((void **)&parent, V * sizeof(int32_t)));
+  MGX_TRY(mgx_bfs_device(ctx, g, nullptr, 1, (int32_t)source, directed, max_depth, mode, hops,
+                         parent, stats));
 
   int64_t *d_out_hops = nullptr, *d_out_parent = nullptr;
   if (out_hops) MGX_TRY(ctx->alloc_async((void **)&d_out_hops, V * sizeof(int64_t)));
@@ -547,27 +627,8 @@ mgx_status mgx_bfs_impl(mgx_context *ctx, mgx_graph *g, int64_t source, int dire
                                  hipMemcpyDeviceToHost, ctx->stream));
   }
   MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  float ms = 0.f;
-  MGX_HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-  MGX_HIP_TRY(hipEventDestroy(ev0));
-  MGX_HIP_TRY(hipEventDestroy(ev1));
-  if (stats) {
-    stats->depth = depth;
-    stats->reached = (int64_t)h.reached;
-    stats->entries_scanned = td_scanned + (int64_t)h.scanned;
-    stats->top_down_levels = td_levels;
-    stats->bottom_up_levels = bu_levels;
-    stats->bottom_up_mask = bu_mask;
-    stats->ms = ms;
-  }
   MGX_TRY(ctx->free_async(hops));
   MGX_TRY(ctx->free_async(parent));
-  MGX_TRY(ctx->free_async(q01));
-  MGX_TRY(ctx->free_async(q23));
-  MGX_TRY(ctx->free_async(visited));
-  MGX_TRY(ctx->free_async(fcur));
-  MGX_TRY(ctx->free_async(fnext));
-  MGX_TRY(ctx->free_async(d_cnt));
   MGX_TRY(ctx->free_async(d_out_hops));
   MGX_TRY(ctx->free_async(d_out_parent));
   MGX_HIP_TRY(hipGetLastError());

@@ -403,6 +403,25 @@ extern "C" mgx_status mgx_bfs(mgx_context *ctx, mgx_graph *g, int64_t source, in
   return mgx_bfs_impl(ctx, g, source, directed, max_depth, mode, out_hops, out_parent, stats);
 }
 
+extern "C" mgx_status mgx_bridges(mgx_context *ctx, mgx_graph *g, int64_t *out_u,
+                                  int64_t *out_v, int64_t *n_bridges,
+                                  mgx_bridges_stats *stats) {
+  MGX_HIP_TRY(hipSetDevice(ctx->device));
+  return mgx_bridges_impl(ctx, g, out_u, out_v, n_bridges, stats);
+}
+
+extern "C" mgx_status mgx_bridges_state(mgx_context *ctx, mgx_graph *g, int64_t *parent,
+                                        int64_t *level, int64_t *pre, int64_t *nd,
+                                        int64_t *low, int64_t *high) {
+  MGX_HIP_TRY(hipSetDevice(ctx->device));
+  return mgx_bridges_state_impl(ctx, g, parent, level, pre, nd, low, high);
+}
+
+extern "C" void mgx_bridges_last_stage_ms(double *forest, double *sorts_scans, double *sweep,
+                                          double *levels) {
+  mgx_bridges_last_stage_ms_impl(forest, sorts_scans, sweep, levels);
+}
+
 extern "C" mgx_status mgx_similarity_pairs(mgx_context *ctx, mgx_graph *g, int metric,
                                            int mode, const int64_t *u, const int64_t *v,
                                            int64_t n_pairs, double *out_sim,

@@ -291,6 +291,10 @@ mgx_status mgx_pagerank_normalize_download(mgx_pagerank_run *run, double *out_ra
 // wcc.hip
 mgx_status mgx_wcc_impl(mgx_context *ctx, mgx_graph *g, int64_t *out_component,
                         int64_t *n_components);
+// Device-output form (bridges.hip): min-member labels, label[v] = smallest id
+// of v's component, in a context allocation of V int32 that the caller frees.
+// Needs V > 0 and the sym-CSR; has synchronized when it returns.
+mgx_status mgx_wcc_labels_device(mgx_context *ctx, mgx_graph *g, int32_t **out_label);
 // katz.hip
 mgx_status mgx_katz_impl(mgx_context *ctx, mgx_graph *g, double alpha, double epsilon,
                          double *out_centrality, int64_t *iterations);
@@ -305,6 +309,23 @@ mgx_status mgx_betweenness_impl(mgx_context *ctx, mgx_graph *g, int directed, in
 mgx_status mgx_bfs_impl(mgx_context *ctx, mgx_graph *g, int64_t source, int directed,
                         int64_t max_depth, int mode, int64_t *out_hops, int64_t *out_parent,
                         mgx_bfs_stats *stats);
+// Device-output form (bridges.hip): level 0 is the n_roots distinct vertices
+// of the device list d_roots (or the one vertex `single` when d_roots is
+// null); hops [V] and parent [V] (nullable) are caller-owned int32 device
+// buffers, left at -1 / INT32_MAX where nothing was reached, parent[root] =
+// root. Same argument checks, direction rule and stats as mgx_bfs.
+mgx_status mgx_bfs_device(mgx_context *ctx, mgx_graph *g, const int32_t *d_roots,
+                          int64_t n_roots, int32_t single, int directed, int64_t max_depth,
+                          int mode, int32_t *hops, int32_t *parent, mgx_bfs_stats *stats);
+
+// bridges.hip
+mgx_status mgx_bridges_impl(mgx_context *ctx, mgx_graph *g, int64_t *out_u, int64_t *out_v,
+                            int64_t *n_bridges, mgx_bridges_stats *stats);
+mgx_status mgx_bridges_state_impl(mgx_context *ctx, mgx_graph *g, int64_t *parent,
+                                  int64_t *level, int64_t *pre, int64_t *nd, int64_t *low,
+                                  int64_t *high);
+void mgx_bridges_last_stage_ms_impl(double *forest, double *sorts_scans, double *sweep,
+                                    double *levels);
 
 // similarity.hip
 mgx_status mgx_similarity_pairs_impl(mgx_context *ctx, mgx_graph *g, int metric, int mode,

@@ -83,18 +83,11 @@ __global__ void k_wcc_emit(int64_t n, const int32_t *label, const uint32_t *scan
 
 }  // namespace
 
-mgx_status mgx_wcc_impl(mgx_context *ctx, mgx_graph *g, int64_t *out_component,
-                        int64_t *n_components) {
-  if (!(g->flags & MGX_BUILD_SYM_CSR)) {
-    mgx_set_error("wcc needs a graph built with MGX_BUILD_SYM_CSR");
-    return MGX_ERR_INVALID_ARGUMENT;
-  }
+// Min-member labels left on the device: *out_label is a context allocation
+// of V int32 that the caller frees (V > 0, sym-CSR present; all work is queued
+// on ctx->stream and the fixpoint loop has synchronized when this returns).
+mgx_status mgx_wcc_labels_device(mgx_context *ctx, mgx_graph *g, int32_t **out_label) {
   const int64_t V = g->n_vertices;
-  if (V == 0) {
-    if (n_components) *n_components = 0;
-    return MGX_OK;
-  }
-
   int32_t *label = nullptr;
   uint32_t *d_changed = nullptr;
   MGX_TRY(ctx->alloc_async((void **)&label, V * sizeof(int32_t)));
@@ -120,6 +113,25 @@ mgx_status mgx_wcc_impl(mgx_context *ctx, mgx_graph *g, int64_t *out_component,
                                ctx->stream));
     MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
   }
+  MGX_TRY(ctx->free_async(d_changed));
+  *out_label = label;
+  return MGX_OK;
+}
+
+mgx_status mgx_wcc_impl(mgx_context *ctx, mgx_graph *g, int64_t *out_component,
+                        int64_t *n_components) {
+  if (!(g->flags & MGX_BUILD_SYM_CSR)) {
+    mgx_set_error("wcc needs a graph built with MGX_BUILD_SYM_CSR");
+    return MGX_ERR_INVALID_ARGUMENT;
+  }
+  const int64_t V = g->n_vertices;
+  if (V == 0) {
+    if (n_components) *n_components = 0;
+    return MGX_OK;
+  }
+
+  int32_t *label = nullptr;
+  MGX_TRY(mgx_wcc_labels_device(ctx, g, &label));
 
   // Renumber + count.
   uint32_t *flag = nullptr, *scan = nullptr;
@@ -151,7 +163,6 @@ mgx_status mgx_wcc_impl(mgx_context *ctx, mgx_graph *g, int64_t *out_component,
   }
   MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
   MGX_TRY(ctx->free_async(label));
-  MGX_TRY(ctx->free_async(d_changed));
   MGX_TRY(ctx->free_async(flag));
   MGX_TRY(ctx->free_async(scan));
   MGX_TRY(ctx->free_async(d_out));

@@ -51,6 +51,18 @@ class BfsStats(ctypes.Structure):
     ]
 
 
+class BridgesStats(ctypes.Structure):
+    _fields_ = [
+        ("bridges", ctypes.c_int64),
+        ("trees", ctypes.c_int64),
+        ("depth", ctypes.c_int64),
+        ("nontree_entries", ctypes.c_int64),
+        ("level_launches", ctypes.c_int64),
+        ("forest_ms", ctypes.c_double),
+        ("ms", ctypes.c_double),
+    ]
+
+
 SIM_JACCARD = 0
 SIM_OVERLAP = 1
 SIM_AUTO = 0
@@ -251,6 +263,39 @@ class Native:
                                                       max_depth, mode, want_parent)
         self._check(status, "mgx_bfs")
         return hops, parent, stats
+
+    def bridges_status(self, ctx, g, n_vertices):
+        """Raw call: (status, pairs[k,2], stats) without raising."""
+        u = np.full(max(n_vertices, 1), -1, dtype=np.int64)
+        v = np.full(max(n_vertices, 1), -1, dtype=np.int64)
+        n = ctypes.c_int64(0)
+        stats = BridgesStats()
+        status = self.lib.mgx_bridges(ctx, g, u.ctypes.data_as(_I64), v.ctypes.data_as(_I64),
+                                      ctypes.byref(n), ctypes.byref(stats))
+        pairs = np.stack([u[:n.value], v[:n.value]], axis=1)
+        return status, pairs, stats
+
+    def bridges(self, ctx, g, n_vertices):
+        """Bridges as (u < v) rows sorted by (u, v), and the call's stats."""
+        status, pairs, stats = self.bridges_status(ctx, g, n_vertices)
+        self._check(status, "mgx_bridges")
+        return pairs, stats
+
+    def bridges_state(self, ctx, g, n_vertices):
+        """Test support: dict of the int64 [V] arrays parent, level, pre, nd, low, high."""
+        names = ("parent", "level", "pre", "nd", "low", "high")
+        out = {k: np.full(n_vertices, -1, dtype=np.int64) for k in names}
+        self._check(
+            self.lib.mgx_bridges_state(ctx, g, *[out[k].ctypes.data_as(_I64) for k in names]),
+            "mgx_bridges_state")
+        return out
+
+    def bridges_last_stage_ms(self):
+        """Split of this thread's last bridges call: forest, sorts_scans, sweep, levels."""
+        vals = [ctypes.c_double() for _ in range(4)]
+        self.lib.mgx_bridges_last_stage_ms.restype = None
+        self.lib.mgx_bridges_last_stage_ms(*[ctypes.byref(x) for x in vals])
+        return dict(zip(("forest", "sorts_scans", "sweep", "levels"), (x.value for x in vals)))
 
     def similarity_pairs_status(self, ctx, g, u, v, metric, mode=SIM_AUTO):
         """Raw call: (status, sim, common, stats) without raising."""
