@@ -137,11 +137,12 @@ mgx_status mgx_betweenness_impl(mgx_context *ctx, mgx_graph *g, int directed, in
   unsigned long long *sigma = nullptr;
   double *dep = nullptr, *bc = nullptr;
   uint32_t *d_changed = nullptr;
-  MGX_TRY(ctx->alloc_async((void **)&dist, batch * V * sizeof(int32_t)));
-  MGX_TRY(ctx->alloc_async((void **)&sigma, batch * V * sizeof(unsigned long long)));
-  MGX_TRY(ctx->alloc_async((void **)&dep, batch * V * sizeof(double)));
-  MGX_TRY(ctx->alloc_async((void **)&bc, V * sizeof(double)));
-  MGX_TRY(ctx->alloc_async((void **)&d_changed, 4));
+  mgx_scope bufs(ctx);
+  MGX_TRY(bufs.alloc(&dist, batch * V));
+  MGX_TRY(bufs.alloc(&sigma, batch * V));
+  MGX_TRY(bufs.alloc(&dep, batch * V));
+  MGX_TRY(bufs.alloc(&bc, V));
+  MGX_TRY(bufs.alloc(&d_changed, 1));
   MGX_HIP_TRY(hipMemsetAsync(bc, 0, V * sizeof(double), ctx->stream));
 
   for (int64_t s0 = 0; s0 < V; s0 += batch) {
@@ -192,11 +193,6 @@ mgx_status mgx_betweenness_impl(mgx_context *ctx, mgx_graph *g, int directed, in
                                ctx->stream));
   }
   MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  MGX_TRY(ctx->free_async(dist));
-  MGX_TRY(ctx->free_async(sigma));
-  MGX_TRY(ctx->free_async(dep));
-  MGX_TRY(ctx->free_async(bc));
-  MGX_TRY(ctx->free_async(d_changed));
   MGX_HIP_TRY(hipGetLastError());
   return MGX_OK;
 }

@@ -416,12 +416,13 @@ mgx_status mgx_bfs_device(mgx_context *ctx, mgx_graph *g, const int32_t *d_roots
   int32_t *q01 = nullptr, *q23 = nullptr;
   uint32_t *visited = nullptr, *fcur = nullptr, *fnext = nullptr;
   BfsCounters *d_cnt = nullptr;
-  MGX_TRY(ctx->alloc_async((void **)&q01, V * sizeof(int32_t)));
-  MGX_TRY(ctx->alloc_async((void **)&q23, V * sizeof(int32_t)));
-  MGX_TRY(ctx->alloc_async((void **)&visited, W * sizeof(uint32_t)));
-  MGX_TRY(ctx->alloc_async((void **)&fcur, W * sizeof(uint32_t)));
-  MGX_TRY(ctx->alloc_async((void **)&fnext, W * sizeof(uint32_t)));
-  MGX_TRY(ctx->alloc_async((void **)&d_cnt, sizeof(BfsCounters)));
+  mgx_scope bufs(ctx);
+  MGX_TRY(bufs.alloc(&q01, V));
+  MGX_TRY(bufs.alloc(&q23, V));
+  MGX_TRY(bufs.alloc(&visited, W));
+  MGX_TRY(bufs.alloc(&fcur, W));
+  MGX_TRY(bufs.alloc(&fnext, W));
+  MGX_TRY(bufs.alloc(&d_cnt, 1));
 
   hipEvent_t ev0, ev1;
   MGX_HIP_TRY(hipEventCreate(&ev0));
@@ -588,12 +589,6 @@ mgx_status mgx_bfs_device(mgx_context *ctx, mgx_graph *g, const int32_t *d_roots
     stats->bottom_up_mask = bu_mask;
     stats->ms = ms;
   }
-  MGX_TRY(ctx->free_async(q01));
-  MGX_TRY(ctx->free_async(q23));
-  MGX_TRY(ctx->free_async(visited));
-  MGX_TRY(ctx->free_async(fcur));
-  MGX_TRY(ctx->free_async(fnext));
-  MGX_TRY(ctx->free_async(d_cnt));
   MGX_HIP_TRY(hipGetLastError());
   return MGX_OK;
 }
@@ -607,15 +602,16 @@ mgx_status mgx_bfs_impl(mgx_context *ctx, mgx_graph *g, int64_t source, int dire
     mgx_set_error("bfs: source %lld outside [0,%lld)", (long long)source, (long long)V);
     return MGX_ERR_INVALID_ARGUMENT;
   }
+  mgx_scope bufs(ctx);
   int32_t *hops = nullptr, *parent = nullptr;
-  MGX_TRY(ctx->alloc_async((void **)&hops, V * sizeof(int32_t)));
-  if (out_parent) MGX_TRY(ctx->alloc_async((void **)&parent, V * sizeof(int32_t)));
+  MGX_TRY(bufs.alloc(&hops, V));
+  if (out_parent) MGX_TRY(bufs.alloc(&parent, V));
   MGX_TRY(mgx_bfs_device(ctx, g, nullptr, 1, (int32_t)source, directed, max_depth, mode, hops,
                          parent, stats));
 
   int64_t *d_out_hops = nullptr, *d_out_parent = nullptr;
-  if (out_hops) MGX_TRY(ctx->alloc_async((void **)&d_out_hops, V * sizeof(int64_t)));
-  if (out_parent) MGX_TRY(ctx->alloc_async((void **)&d_out_parent, V * sizeof(int64_t)));
+  if (out_hops) MGX_TRY(bufs.alloc(&d_out_hops, V));
+  if (out_parent) MGX_TRY(bufs.alloc(&d_out_parent, V));
   if (out_hops || out_parent) {
     hipLaunchKernelGGL(k_bfs_emit, dim3((uint32_t)grid_for(V, kGridCap)), dim3(kBlock), 0,
                        ctx->stream, V, hops, parent, d_out_hops, d_out_parent);
@@ -627,10 +623,6 @@ mgx_status mgx_bfs_impl(mgx_context *ctx, mgx_graph *g, int64_t source, int dire
                                  hipMemcpyDeviceToHost, ctx->stream));
   }
   MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  MGX_TRY(ctx->free_async(hops));
-  MGX_TRY(ctx->free_async(parent));
-  MGX_TRY(ctx->free_async(d_out_hops));
-  MGX_TRY(ctx->free_async(d_out_parent));
   MGX_HIP_TRY(hipGetLastError());
   return MGX_OK;
 }

@@ -43,7 +43,6 @@
 // parent entries may straddle lanes and waves, so it is counted with the
 // row reduction.
 
-#include <algorithm>
 #include <climits>
 #include <cstring>
 #include <vector>
@@ -260,22 +259,6 @@ __global__ void k_br_unpack_pairs(int64_t n, const uint64_t *keys, int64_t *u, i
 #undef BR_FOR
 #undef BR_FOR_WAVES
 
-// Context allocations released together.
-struct Bufs {
-  mgx_context *ctx;
-  std::vector<void *> ptrs;
-  explicit Bufs(mgx_context *c) : ctx(c) {}
-  ~Bufs() {
-    for (void *p : ptrs) (void)ctx->free_async(p);
-  }
-  template <typename T>
-  mgx_status alloc(T **p, int64_t count) {
-    MGX_TRY(ctx->alloc_async((void **)p, (size_t)std::max<int64_t>(count, 1) * sizeof(T)));
-    ptrs.push_back(*p);
-    return MGX_OK;
-  }
-};
-
 // Stage boundaries of the last call on this thread.
 enum { kStForest, kStSorts, kStSweep, kStLevels, kStages };
 thread_local double t_stage_ms[kStages] = {0, 0, 0, 0};
@@ -326,7 +309,7 @@ struct BridgeState {
 inline uint32_t grid1(int64_t n) { return (uint32_t)grid_for(n, 2048); }
 
 // Steps 1-6: everything up to the folded low/high. V > 0, sym-CSR present.
-mgx_status bridges_compute(mgx_context *ctx, mgx_graph *g, Bufs &B, Timeline &T,
+mgx_status bridges_compute(mgx_context *ctx, mgx_graph *g, mgx_scope &B, Timeline &T,
                            BridgeState &S) {
   const int64_t V = g->n_vertices;
   hipStream_t st = ctx->stream;
@@ -339,8 +322,7 @@ mgx_status bridges_compute(mgx_context *ctx, mgx_graph *g, Bufs &B, Timeline &T,
   MGX_TRY(B.alloc(&roots, V));
   {
     int32_t *label = nullptr;
-    MGX_TRY(mgx_wcc_labels_device(ctx, g, &label));
-    B.ptrs.push_back(label);
+    MGX_TRY(mgx_wcc_labels_device(B, g, &label));
     hipLaunchKernelGGL(k_br_flag_roots, dim3(grid1(V)), dim3(kBlock), 0, st, V, label, S.flag);
   }
   MGX_TRY(mgx_with_temp(ctx, "bridges root scan", [&](void *tmp, size_t &bytes) {
@@ -511,7 +493,7 @@ mgx_status mgx_bridges_impl(mgx_context *ctx, mgx_graph *g, int64_t *out_u, int6
   if (n_bridges) *n_bridges = 0;
   if (V == 0) return MGX_OK;
 
-  Bufs B(ctx);
+  mgx_scope B(ctx);
   Timeline T(ctx->stream);
   BridgeState S;
   MGX_TRY(T.mark(kStForest));
@@ -583,7 +565,7 @@ mgx_status mgx_bridges_state_impl(mgx_context *ctx, mgx_graph *g, int64_t *paren
   MGX_TRY(check_sym(g));
   const int64_t V = g->n_vertices;
   if (V == 0) return MGX_OK;
-  Bufs B(ctx);
+  mgx_scope B(ctx);
   Timeline T(ctx->stream);
   BridgeState S;
   MGX_TRY(T.mark(kStForest));

@@ -160,9 +160,10 @@ mgx_status build_sorted_cols(mgx_context *ctx, const int32_t *d_src, const int32
                              bool ranged, int32_t lo, int32_t hi, int32_t *col,
                              int64_t col_count) {
   if (n_edges == 0) return MGX_OK;
+  mgx_scope bufs(ctx);
   uint64_t *keys = nullptr, *keys_out = nullptr;
-  MGX_TRY(ctx->alloc_async((void **)&keys, n_edges * sizeof(uint64_t)));
-  MGX_TRY(ctx->alloc_async((void **)&keys_out, n_edges * sizeof(uint64_t)));
+  MGX_TRY(bufs.alloc(&keys, n_edges));
+  MGX_TRY(bufs.alloc(&keys_out, n_edges));
   if (ranged) {
     hipLaunchKernelGGL(k_pack_pairs_ranged, dim3(grid_for(n_edges)), dim3(kBlock), 0,
                        ctx->stream, n_edges, d_src, d_dst, lo, hi, keys);
@@ -179,8 +180,6 @@ mgx_status build_sorted_cols(mgx_context *ctx, const int32_t *d_src, const int32
   }));
   hipLaunchKernelGGL(k_unpack_cols, dim3(grid_for(col_count)), dim3(kBlock), 0, ctx->stream,
                      col_count, keys_out, col);
-  MGX_TRY(ctx->free_async(keys));
-  MGX_TRY(ctx->free_async(keys_out));
   return MGX_OK;
 }
 
@@ -193,11 +192,12 @@ mgx_status build_sorted_cols_w(mgx_context *ctx, const int32_t *d_src,
                                const int32_t *d_dst, const float *d_w, int64_t n_edges,
                                int64_t key_rows, int32_t *col, float *out_w) {
   if (n_edges == 0) return MGX_OK;
+  mgx_scope bufs(ctx);
   uint64_t *keys = nullptr, *keys_out = nullptr;
   float *vals_out = nullptr;
-  MGX_TRY(ctx->alloc_async((void **)&keys, n_edges * sizeof(uint64_t)));
-  MGX_TRY(ctx->alloc_async((void **)&keys_out, n_edges * sizeof(uint64_t)));
-  MGX_TRY(ctx->alloc_async((void **)&vals_out, n_edges * sizeof(float)));
+  MGX_TRY(bufs.alloc(&keys, n_edges));
+  MGX_TRY(bufs.alloc(&keys_out, n_edges));
+  MGX_TRY(bufs.alloc(&vals_out, n_edges));
   hipLaunchKernelGGL(k_pack_pairs, dim3(grid_for(n_edges)), dim3(kBlock), 0, ctx->stream,
                      n_edges, d_src, d_dst, (const int32_t *)nullptr, keys);
   int end_bit = 33;
@@ -210,9 +210,6 @@ mgx_status build_sorted_cols_w(mgx_context *ctx, const int32_t *d_src,
                      n_edges, keys_out, col);
   MGX_HIP_TRY(hipMemcpyAsync(out_w, vals_out, n_edges * sizeof(float),
                              hipMemcpyDeviceToDevice, ctx->stream));
-  MGX_TRY(ctx->free_async(keys));
-  MGX_TRY(ctx->free_async(keys_out));
-  MGX_TRY(ctx->free_async(vals_out));
   return MGX_OK;
 }
 
@@ -239,13 +236,14 @@ mgx_status build_sorted_sym(mgx_context *ctx, const int32_t *d_src, const int32_
                             int32_t *col, float *out_w) {
   if (n_edges == 0) return MGX_OK;
   const int64_t n2 = 2 * n_edges;
+  mgx_scope bufs(ctx);
   uint64_t *keys = nullptr, *keys_out = nullptr;
   float *vals = nullptr, *vals_out = nullptr;
-  MGX_TRY(ctx->alloc_async((void **)&keys, n2 * sizeof(uint64_t)));
-  MGX_TRY(ctx->alloc_async((void **)&keys_out, n2 * sizeof(uint64_t)));
+  MGX_TRY(bufs.alloc(&keys, n2));
+  MGX_TRY(bufs.alloc(&keys_out, n2));
   if (out_w) {
-    MGX_TRY(ctx->alloc_async((void **)&vals, n2 * sizeof(float)));
-    MGX_TRY(ctx->alloc_async((void **)&vals_out, n2 * sizeof(float)));
+    MGX_TRY(bufs.alloc(&vals, n2));
+    MGX_TRY(bufs.alloc(&vals_out, n2));
   }
   hipLaunchKernelGGL(k_pack_sym, dim3(grid_for(n_edges)), dim3(kBlock), 0, ctx->stream,
                      n_edges, d_src, d_dst, d_w, keys, vals);
@@ -263,10 +261,6 @@ mgx_status build_sorted_sym(mgx_context *ctx, const int32_t *d_src, const int32_
     MGX_HIP_TRY(hipMemcpyAsync(out_w, vals_out, n2 * sizeof(float),
                                hipMemcpyDeviceToDevice, ctx->stream));
   }
-  MGX_TRY(ctx->free_async(keys));
-  MGX_TRY(ctx->free_async(keys_out));
-  if (vals) MGX_TRY(ctx->free_async(vals));
-  if (vals_out) MGX_TRY(ctx->free_async(vals_out));
   return MGX_OK;
 }
 
@@ -336,19 +330,20 @@ mgx_status mgx_gen_weights_device(mgx_context *ctx, int64_t n_edges, uint64_t se
   return MGX_OK;
 }
 
-mgx_status mgx_build_bins_range(mgx_context *ctx, const uint32_t *lo, const uint32_t *hi,
+mgx_status mgx_build_bins_range(mgx_scope &own, const uint32_t *lo, const uint32_t *hi,
                                 int64_t rows, bool include_zero, mgx_bins *bins) {
-  if (rows == 0) {
-    bins->rows = nullptr;
-    return MGX_OK;
-  }
-  MGX_HIP_TRY(mgx_hip_malloc(&bins->rows, rows * sizeof(int32_t)));
+  mgx_context *ctx = own.ctx;
+  bins->rows = nullptr;
+  if (rows == 0) return MGX_OK;
+  int32_t *list = nullptr;
+  MGX_TRY(own.alloc_plain(&list, rows));
+  mgx_scope bufs(ctx);
   uint32_t *keys = nullptr, *keys_out = nullptr, *vals = nullptr;
-  MGX_HIP_TRY(mgx_hip_malloc(&keys, rows * sizeof(uint32_t)));
-  MGX_HIP_TRY(mgx_hip_malloc(&keys_out, rows * sizeof(uint32_t)));
-  MGX_HIP_TRY(mgx_hip_malloc(&vals, rows * sizeof(uint32_t)));
+  MGX_TRY(bufs.alloc_plain(&keys, rows));
+  MGX_TRY(bufs.alloc_plain(&keys_out, rows));
+  MGX_TRY(bufs.alloc_plain(&vals, rows));
   uint32_t *counts6 = nullptr;
-  MGX_HIP_TRY(mgx_hip_malloc(&counts6, 6 * sizeof(uint32_t)));
+  MGX_TRY(bufs.alloc_plain(&counts6, 6));
   MGX_HIP_TRY(hipMemsetAsync(counts6, 0, 24, ctx->stream));
 
   hipLaunchKernelGGL(k_bin_keys, dim3(grid_for(rows)), dim3(kBlock), 0, ctx->stream, rows,
@@ -361,7 +356,7 @@ mgx_status mgx_build_bins_range(mgx_context *ctx, const uint32_t *lo, const uint
   // lands past the used prefix.
   MGX_TRY(mgx_with_temp(ctx, "degree-bin sort", [&](void *tmp, size_t &bytes) {
     return rocprim::radix_sort_pairs(tmp, bytes, keys, keys_out, vals,
-                                     (uint32_t *)bins->rows, rows, 0, 3, ctx->stream);
+                                     (uint32_t *)list, rows, 0, 3, ctx->stream);
   }));
 
   uint32_t h_counts[6] = {0, 0, 0, 0, 0, 0};
@@ -373,11 +368,15 @@ mgx_status mgx_build_bins_range(mgx_context *ctx, const uint32_t *lo, const uint
   bins->count[0] = (int64_t)h_counts[0] + h_counts[1];
   for (int b = 1; b < 4; ++b) bins->count[b] = h_counts[b + 1];
   for (int b = 0; b < 4; ++b) bins->grid[b] = mgx_bin_grid(b, bins->count[b]);
+  bins->rows = list;
+  return MGX_OK;
+}
 
-  MGX_HIP_TRY(hipFree(keys));
-  MGX_HIP_TRY(hipFree(keys_out));
-  MGX_HIP_TRY(hipFree(vals));
-  MGX_HIP_TRY(hipFree(counts6));
+mgx_status mgx_build_bins_range(mgx_context *ctx, const uint32_t *lo, const uint32_t *hi,
+                                int64_t rows, bool include_zero, mgx_bins *bins) {
+  mgx_scope own(ctx);
+  MGX_TRY(mgx_build_bins_range(own, lo, hi, rows, include_zero, bins));
+  (void)own.give_up(bins->rows);
   return MGX_OK;
 }
 
@@ -579,8 +578,9 @@ mgx_status mgx_build_from_device_coo(mgx_context *ctx, const int32_t *d_src,
   MGX_HIP_TRY(hipEventCreate(&ev1));
   MGX_HIP_TRY(hipEventRecord(ev0, ctx->stream));
 
+  mgx_scope bufs(ctx);
   uint32_t *counts = nullptr;
-  MGX_HIP_TRY(mgx_hip_malloc(&counts, (V > 0 ? V : 1) * sizeof(uint32_t)));
+  MGX_TRY(bufs.alloc_plain(&counts, V));
 
   // out-degree (+ inv) — always needed by PageRank/Katz result paths.
   MGX_HIP_TRY(mgx_hip_malloc(&g->out_degree, (V > 0 ? V : 1) * sizeof(uint32_t)));
@@ -613,12 +613,13 @@ mgx_status mgx_build_from_device_coo(mgx_context *ctx, const int32_t *d_src,
     // pack into the lowest addresses (L2/L3-resident under power-law skew).
     int32_t *d_perm = nullptr;
     MGX_HIP_TRY(mgx_hip_malloc(&g->order, (V > 0 ? V : 1) * sizeof(int32_t)));
-    MGX_HIP_TRY(mgx_hip_malloc(&d_perm, (V > 0 ? V : 1) * sizeof(int32_t)));
+    MGX_TRY(bufs.alloc_plain(&d_perm, V));
     {
+      mgx_scope sort_bufs(ctx);
       uint32_t *deg_sorted = nullptr;
       int32_t *iota = nullptr;
-      MGX_HIP_TRY(mgx_hip_malloc(&deg_sorted, (V > 0 ? V : 1) * sizeof(uint32_t)));
-      MGX_HIP_TRY(mgx_hip_malloc(&iota, (V > 0 ? V : 1) * sizeof(int32_t)));
+      MGX_TRY(sort_bufs.alloc_plain(&deg_sorted, V));
+      MGX_TRY(sort_bufs.alloc_plain(&iota, V));
       hipLaunchKernelGGL(mgx_k_iota<int32_t>, dim3(grid_for(V)), dim3(kBlock), 0,
                          ctx->stream, V, iota);
       MGX_TRY(mgx_with_temp(ctx, "hot-first degree sort", [&](void *tmp, size_t &bytes) {
@@ -642,8 +643,6 @@ mgx_status mgx_build_from_device_coo(mgx_context *ctx, const int32_t *d_src,
                          g->order, d_perm);
       hipLaunchKernelGGL(k_inv_outdeg, dim3(grid_for(V)), dim3(kBlock), 0, ctx->stream, V,
                          g->out_degree, g->inv_outdeg);
-      MGX_HIP_TRY(hipFree(deg_sorted));
-      MGX_HIP_TRY(hipFree(iota));
     }
     MGX_HIP_TRY(hipMemsetAsync(counts, 0, V * sizeof(uint32_t), ctx->stream));
     hipLaunchKernelGGL(k_hist_perm, dim3(grid_for(E)), dim3(kBlock), 0, ctx->stream, E,
@@ -652,7 +651,7 @@ mgx_status mgx_build_from_device_coo(mgx_context *ctx, const int32_t *d_src,
     MGX_TRY(scan_counts(ctx, counts, V, g->in_row_ptr));
     MGX_HIP_TRY(mgx_hip_malloc(&g->in_col, (E > 0 ? E : 1) * sizeof(int32_t)));
     MGX_TRY(build_sorted_cols(ctx, d_src, d_dst, d_perm, E, V, false, 0, 0, g->in_col, E));
-    MGX_HIP_TRY(hipFree(d_perm));
+    bufs.release(d_perm);
     MGX_TRY(mgx_build_bins(ctx, g->in_row_ptr, V, &g->bins_in));
     MGX_TRY(mgx_build_stripes(ctx, g));
   }
@@ -686,7 +685,7 @@ mgx_status mgx_build_from_device_coo(mgx_context *ctx, const int32_t *d_src,
     MGX_TRY(mgx_build_bins(ctx, g->sym_row_ptr, V, &g->bins_sym));
   }
 
-  MGX_HIP_TRY(hipFree(counts));
+  bufs.release(counts);
   MGX_HIP_TRY(hipEventRecord(ev1, ctx->stream));
   MGX_HIP_TRY(hipEventSynchronize(ev1));
   float ms = 0.f;
@@ -724,8 +723,9 @@ mgx_status mgx_build_sharded_in_csr(mgx_context *ctx, const int32_t *d_src,
   hipLaunchKernelGGL(k_inv_outdeg, dim3(grid_for(V)), dim3(kBlock), 0, ctx->stream, V,
                      g->out_degree, g->inv_outdeg);
 
+  mgx_scope bufs(ctx);
   uint32_t *counts = nullptr;
-  MGX_HIP_TRY(mgx_hip_malloc(&counts, (rows > 0 ? rows : 1) * sizeof(uint32_t)));
+  MGX_TRY(bufs.alloc_plain(&counts, rows));
   MGX_HIP_TRY(hipMemsetAsync(counts, 0, rows * sizeof(uint32_t), ctx->stream));
   hipLaunchKernelGGL(k_hist_ranged, dim3(grid_for(E)), dim3(kBlock), 0, ctx->stream, E,
                      d_dst, (int32_t)row_begin, (int32_t)row_end, counts);
@@ -741,7 +741,7 @@ mgx_status mgx_build_sharded_in_csr(mgx_context *ctx, const int32_t *d_src,
                             (int32_t)row_end, g->in_col, local_edges));
   MGX_TRY(mgx_build_bins(ctx, g->in_row_ptr, rows, &g->bins_in));
   MGX_TRY(mgx_build_stripes(ctx, g));
-  MGX_HIP_TRY(hipFree(counts));
+  bufs.release(counts);
 
   MGX_HIP_TRY(hipEventRecord(ev1, ctx->stream));
   MGX_HIP_TRY(hipEventSynchronize(ev1));
@@ -754,23 +754,26 @@ mgx_status mgx_build_sharded_in_csr(mgx_context *ctx, const int32_t *d_src,
   return MGX_OK;
 }
 
-// Host COO (int64/double) upload helpers, used by mgx_graph_from_coo.
-mgx_status mgx_upload_coo(mgx_context *ctx, const int64_t *src, const int64_t *dst,
+// Host COO (int64/double) upload helpers, used by mgx_graph_from_coo. The
+// device COO belongs to the caller's scope `own`.
+mgx_status mgx_upload_coo(mgx_scope &own, const int64_t *src, const int64_t *dst,
                           const double *weights, int64_t n_edges, int32_t **d_src,
                           int32_t **d_dst, float **d_w) {
-  MGX_HIP_TRY(mgx_hip_malloc(d_src, (n_edges > 0 ? n_edges : 1) * sizeof(int32_t)));
-  MGX_HIP_TRY(mgx_hip_malloc(d_dst, (n_edges > 0 ? n_edges : 1) * sizeof(int32_t)));
+  mgx_context *ctx = own.ctx;
+  MGX_TRY(own.alloc_plain(d_src, n_edges));
+  MGX_TRY(own.alloc_plain(d_dst, n_edges));
   *d_w = nullptr;
-  if (weights) MGX_HIP_TRY(mgx_hip_malloc(d_w, (n_edges > 0 ? n_edges : 1) * sizeof(float)));
+  if (weights) MGX_TRY(own.alloc_plain(d_w, n_edges));
 
   // Chunked staging: int64 -> int32 converted on device.
   const int64_t chunk = 16 << 20;
+  mgx_scope stage(ctx);
   int64_t *stage64 = nullptr;
   double *stagef = nullptr;
   const int64_t this_chunk = n_edges < chunk ? n_edges : chunk;
   if (this_chunk > 0) {
-    MGX_HIP_TRY(mgx_hip_malloc(&stage64, this_chunk * sizeof(int64_t)));
-    if (weights) MGX_HIP_TRY(mgx_hip_malloc(&stagef, this_chunk * sizeof(double)));
+    MGX_TRY(stage.alloc_plain(&stage64, this_chunk));
+    if (weights) MGX_TRY(stage.alloc_plain(&stagef, this_chunk));
   }
   for (int64_t off = 0; off < n_edges; off += chunk) {
     const int64_t n = (n_edges - off) < chunk ? (n_edges - off) : chunk;
@@ -791,8 +794,6 @@ mgx_status mgx_upload_coo(mgx_context *ctx, const int64_t *src, const int64_t *d
     // The next chunk reuses the staging buffer: wait for queued copies.
     MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
   }
-  if (stage64) MGX_HIP_TRY(hipFree(stage64));
-  if (stagef) MGX_HIP_TRY(hipFree(stagef));
   return MGX_OK;
 }
 
@@ -803,11 +804,12 @@ extern "C" mgx_status mgx_gen_edges_to_host(mgx_context *ctx, int rmat, int scal
                                             uint64_t seed, double a, double b, double c,
                                             int64_t *out_src, int64_t *out_dst) {
   MGX_HIP_TRY(hipSetDevice(ctx->device));
+  mgx_scope bufs(ctx);
   int32_t *d_src = nullptr, *d_dst = nullptr;
   int64_t *d_wide = nullptr;
-  MGX_HIP_TRY(mgx_hip_malloc(&d_src, (n_edges > 0 ? n_edges : 1) * sizeof(int32_t)));
-  MGX_HIP_TRY(mgx_hip_malloc(&d_dst, (n_edges > 0 ? n_edges : 1) * sizeof(int32_t)));
-  MGX_HIP_TRY(mgx_hip_malloc(&d_wide, (n_edges > 0 ? n_edges : 1) * sizeof(int64_t)));
+  MGX_TRY(bufs.alloc_plain(&d_src, n_edges));
+  MGX_TRY(bufs.alloc_plain(&d_dst, n_edges));
+  MGX_TRY(bufs.alloc_plain(&d_wide, n_edges));
   mgx_status s;
   if (rmat) {
     s = mgx_gen_rmat_device(ctx, scale, n_edges, seed, a, b, c, d_src, d_dst);
@@ -826,8 +828,5 @@ extern "C" mgx_status mgx_gen_edges_to_host(mgx_context *ctx, int rmat, int scal
                          ctx->stream);
     (void)hipStreamSynchronize(ctx->stream);
   }
-  (void)hipFree(d_src);
-  (void)hipFree(d_dst);
-  (void)hipFree(d_wide);
   return s;
 }

@@ -304,8 +304,9 @@ mgx_status kon_grow_slots(mgx_context *ctx, int64_t need) {
   int64_t cap = g_k.slots_cap > 0 ? g_k.slots_cap : 256;
   while (cap < need) cap *= 2;
   auto grow = [&](double **p, double init) -> mgx_status {
+    mgx_scope grown(ctx);
     double *np = nullptr;
-    MGX_HIP_TRY(mgx_hip_malloc(&np, cap * 8));
+    MGX_TRY(grown.alloc_plain(&np, cap));
     hipLaunchKernelGGL(mgx_k_fill<double>, dim3((uint32_t)grid_for(cap)), dim3(kBlock), 0,
                        ctx->stream, cap, init, np);
     if (*p && g_k.slots_cap > 0) {
@@ -316,7 +317,7 @@ mgx_status kon_grow_slots(mgx_context *ctx, int64_t need) {
       MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
       (void)hipFree(*p);
     }
-    *p = np;
+    *p = grown.give_up(np);
     return MGX_OK;
   };
   for (size_t i = 0; i < g_k.omega.size(); ++i)
@@ -325,8 +326,9 @@ mgx_status kon_grow_slots(mgx_context *ctx, int64_t need) {
   MGX_TRY(grow(&g_k.lr, 0.0));
   MGX_TRY(grow(&g_k.ur, 0.0));
   {
+    mgx_scope grown(ctx);
     uint8_t *na = nullptr;
-    MGX_HIP_TRY(mgx_hip_malloc(&na, cap));
+    MGX_TRY(grown.alloc_plain(&na, cap));
     MGX_HIP_TRY(hipMemsetAsync(na, 0, cap, ctx->stream));
     if (g_k.d_active && g_k.slots_cap > 0) {
       MGX_HIP_TRY(hipMemcpyAsync(na, g_k.d_active, g_k.slots_cap,
@@ -334,22 +336,23 @@ mgx_status kon_grow_slots(mgx_context *ctx, int64_t need) {
     }
     MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (g_k.d_active) (void)hipFree(g_k.d_active);
-    g_k.d_active = na;
+    g_k.d_active = grown.give_up(na);
   }
   g_k.slots_cap = cap;
   return MGX_OK;
 }
 
 mgx_status kon_add_iteration(mgx_context *ctx, double omega_init) {
+  mgx_scope fresh(ctx);
   double *w = nullptr, *c = nullptr;
-  MGX_HIP_TRY(mgx_hip_malloc(&w, g_k.slots_cap * 8));
-  MGX_HIP_TRY(mgx_hip_malloc(&c, g_k.slots_cap * 8));
+  MGX_TRY(fresh.alloc_plain(&w, g_k.slots_cap));
+  MGX_TRY(fresh.alloc_plain(&c, g_k.slots_cap));
   hipLaunchKernelGGL(mgx_k_fill<double>, dim3((uint32_t)grid_for(g_k.slots_cap)),
                      dim3(kBlock), 0, ctx->stream, g_k.slots_cap, omega_init, w);
   hipLaunchKernelGGL(mgx_k_fill<double>, dim3((uint32_t)grid_for(g_k.slots_cap)),
                      dim3(kBlock), 0, ctx->stream, g_k.slots_cap, 0.0, c);
-  g_k.omega.push_back(w);
-  g_k.cent.push_back(c);
+  g_k.omega.push_back(fresh.give_up(w));
+  g_k.cent.push_back(fresh.give_up(c));
   return MGX_OK;
 }
 
@@ -430,11 +433,12 @@ mgx_status kon_loop(mgx_context *ctx, mgx_graph *g, const KMaps &m, double gamma
   int32_t *d_act = nullptr, *d_act_sorted = nullptr;
   uint64_t *d_keys = nullptr, *d_keys_sorted = nullptr;
   uint32_t *d_flag = nullptr;
-  MGX_HIP_TRY(mgx_hip_malloc(&d_act, (n_active > 0 ? n_active : 1) * 4));
-  MGX_HIP_TRY(mgx_hip_malloc(&d_act_sorted, (n_active > 0 ? n_active : 1) * 4));
-  MGX_HIP_TRY(mgx_hip_malloc(&d_keys, (n_active > 0 ? n_active : 1) * 8));
-  MGX_HIP_TRY(mgx_hip_malloc(&d_keys_sorted, (n_active > 0 ? n_active : 1) * 8));
-  MGX_HIP_TRY(mgx_hip_malloc(&d_flag, 4));
+  mgx_scope bufs(ctx);
+  MGX_TRY(bufs.alloc_plain(&d_act, n_active));
+  MGX_TRY(bufs.alloc_plain(&d_act_sorted, n_active));
+  MGX_TRY(bufs.alloc_plain(&d_keys, n_active));
+  MGX_TRY(bufs.alloc_plain(&d_keys_sorted, n_active));
+  MGX_TRY(bufs.alloc_plain(&d_flag, 1));
   if (n_active > 0)
     MGX_HIP_TRY(hipMemcpyAsync(d_act, act.data(), n_active * 4, hipMemcpyHostToDevice,
                                ctx->stream));
@@ -492,11 +496,6 @@ mgx_status kon_loop(mgx_context *ctx, mgx_graph *g, const KMaps &m, double gamma
       break;
     }
   }
-  (void)hipFree(d_act);
-  (void)hipFree(d_act_sorted);
-  (void)hipFree(d_keys);
-  (void)hipFree(d_keys_sorted);
-  (void)hipFree(d_flag);
   (void)V;
   return st;
 }
@@ -504,12 +503,12 @@ mgx_status kon_loop(mgx_context *ctx, mgx_graph *g, const KMaps &m, double gamma
 mgx_status kon_output(mgx_context *ctx, const KMaps &m, double *out) {
   if (!out || m.V == 0) return MGX_OK;
   double *d_out = nullptr;
-  MGX_TRY(ctx->alloc_async((void **)&d_out, m.V * 8));
+  mgx_scope bufs(ctx);
+  MGX_TRY(bufs.alloc(&d_out, m.V));
   hipLaunchKernelGGL(k_gather_out, dim3((uint32_t)grid_for(m.V)), dim3(kBlock), 0,
                      ctx->stream, m.V, m.dense2slot, g_k.cent[g_k.iteration], d_out);
   MGX_HIP_TRY(hipMemcpyAsync(out, d_out, m.V * 8, hipMemcpyDeviceToHost, ctx->stream));
   MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  MGX_TRY(ctx->free_async(d_out));
   return MGX_OK;
 }
 
@@ -678,213 +677,197 @@ extern "C" mgx_status mgx_konline_update(mgx_context *ctx, mgx_graph *g,
       pair_cnt.push_back(c);
     }
   }
-  uint64_t *d_pairs = nullptr;
-  uint32_t *d_cnt = nullptr;
-  MGX_HIP_TRY(mgx_hip_malloc(&d_pairs, (pair_keys.empty() ? 1 : pair_keys.size()) * 8));
-  MGX_HIP_TRY(mgx_hip_malloc(&d_cnt, (pair_cnt.empty() ? 1 : pair_cnt.size()) * 4));
-  if (!pair_keys.empty()) {
-    MGX_HIP_TRY(hipMemcpyAsync(d_pairs, pair_keys.data(), pair_keys.size() * 8,
-                               hipMemcpyHostToDevice, ctx->stream));
-    MGX_HIP_TRY(hipMemcpyAsync(d_cnt, pair_cnt.data(), pair_cnt.size() * 4,
-                               hipMemcpyHostToDevice, ctx->stream));
-  }
-
-  // edge term slot arrays
-  std::vector<int32_t> new_ws, new_vs, del_ws, del_vs;
-  for (int64_t i = 0; i < n_ce; ++i) {
-    auto w = g_k.mg2slot.find(created_e[2 * i]);
-    auto v = g_k.mg2slot.find(created_e[2 * i + 1]);
-    if (w == g_k.mg2slot.end() || v == g_k.mg2slot.end()) continue;
-    new_ws.push_back(w->second);
-    new_vs.push_back(v->second);
-  }
-  for (int64_t i = 0; i < n_de; ++i) {
-    auto w = g_k.mg2slot.find(deleted_e[2 * i]);
-    auto v = g_k.mg2slot.find(deleted_e[2 * i + 1]);
-    if (w == g_k.mg2slot.end() || v == g_k.mg2slot.end()) continue;
-    del_ws.push_back(w->second);
-    del_vs.push_back(v->second);
-  }
-  auto upload_i32 = [&](const std::vector<int32_t> &v, int32_t **d) -> mgx_status {
-    MGX_HIP_TRY(mgx_hip_malloc(d, (v.empty() ? 1 : v.size()) * 4));
-    if (!v.empty())
-      MGX_HIP_TRY(hipMemcpyAsync(*d, v.data(), v.size() * 4, hipMemcpyHostToDevice,
-                                 ctx->stream));
-    return MGX_OK;
-  };
-  int32_t *d_new_ws = nullptr, *d_new_vs = nullptr, *d_del_ws = nullptr,
-          *d_del_vs = nullptr;
-  MGX_TRY(upload_i32(new_ws, &d_new_ws));
-  MGX_TRY(upload_i32(new_vs, &d_new_vs));
-  MGX_TRY(upload_i32(del_ws, &d_del_ws));
-  MGX_TRY(upload_i32(del_vs, &d_del_vs));
-
-  // context_new omegas: new_omega[0] = 1 for all current nodes; levels
-  // 1..iteration computed below. Keep as separate device arrays.
-  std::vector<double *> new_omega(g_k.iteration + 1, nullptr);
-  auto cleanup_new = [&]() {
-    for (auto p : new_omega)
-      if (p) (void)hipFree(p);
-  };
-  for (int64_t i = 0; i <= g_k.iteration; ++i) {
-    if (mgx_hip_malloc(&new_omega[i], g_k.slots_cap * 8) != hipSuccess) {
-      cleanup_new();
-      mgx_set_error("konline_update: out of memory for level omegas");
-      return MGX_ERR_OUT_OF_MEMORY;
-    }
-  }
-  hipLaunchKernelGGL(mgx_k_fill<double>, dim3((uint32_t)grid_for(g_k.slots_cap)),
-                     dim3(kBlock), 0, ctx->stream, g_k.slots_cap, 1.0, new_omega[0]);
-
-  // updated/frontier state in dense space
-  uint32_t *d_updated = nullptr;
-  int32_t *d_front = nullptr, *d_next = nullptr;
-  unsigned long long *d_nn = nullptr;
-  MGX_HIP_TRY(mgx_hip_malloc(&d_updated, V * 4));
-  MGX_HIP_TRY(mgx_hip_malloc(&d_front, V * 4));
-  MGX_HIP_TRY(mgx_hip_malloc(&d_next, V * 4));
-  MGX_HIP_TRY(mgx_hip_malloc(&d_nn, 8));
-  std::vector<uint32_t> upd_h(V, 0);
-  std::vector<int32_t> front_h;
-  for (auto mg : updated_mg) {
-    auto it = mg2dense.find(mg);
-    if (it == mg2dense.end()) continue;  // deleted endpoint: not a graph node
-    if (!upd_h[it->second]) {
-      upd_h[it->second] = 1;
-      front_h.push_back(it->second);
-    }
-  }
-
-  for (int64_t lvl = 1; lvl <= g_k.iteration; ++lvl) {
-    // new_omega[lvl] = old omega[lvl] (:266-268; only current slots matter)
-    MGX_HIP_TRY(hipMemcpyAsync(new_omega[lvl], g_k.omega[lvl], g_k.slots_cap * 8,
-                               hipMemcpyDeviceToDevice, ctx->stream));
-    MGX_HIP_TRY(hipMemcpyAsync(d_updated, upd_h.data(), V * 4,
-                               hipMemcpyHostToDevice, ctx->stream));
-    // frontier rounds: every updated node processes its out-edges exactly
-    // once per level; nodes marked mid-level join later rounds
-    std::vector<int32_t> front = front_h;
-    MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    while (!front.empty()) {
-      MGX_HIP_TRY(hipMemcpyAsync(d_front, front.data(), front.size() * 4,
+  // The device temporaries of the update: gone before the loop allocates.
+  {
+    mgx_scope bufs(ctx);
+    uint64_t *d_pairs = nullptr;
+    uint32_t *d_cnt = nullptr;
+    MGX_TRY(bufs.alloc_plain(&d_pairs, (int64_t)pair_keys.size()));
+    MGX_TRY(bufs.alloc_plain(&d_cnt, (int64_t)pair_cnt.size()));
+    if (!pair_keys.empty()) {
+      MGX_HIP_TRY(hipMemcpyAsync(d_pairs, pair_keys.data(), pair_keys.size() * 8,
                                  hipMemcpyHostToDevice, ctx->stream));
-      MGX_HIP_TRY(hipMemsetAsync(d_nn, 0, 8, ctx->stream));
-      LevelArgs L;
-      L.front = d_front;
-      L.n_front = (int64_t)front.size();
-      L.out_row_ptr = g->out_row_ptr;
-      L.out_col = g->out_col;
-      L.dense2slot = m.dense2slot;
-      L.omega_new_prev = new_omega[lvl - 1];
-      L.omega_old_prev = g_k.omega[lvl - 1];
-      L.omega_new_cur = new_omega[lvl];
-      L.updated = d_updated;
-      L.next = d_next;
-      L.n_next = d_nn;
-      L.new_pairs = d_pairs;
-      L.new_cnt = d_cnt;
-      L.n_new_pairs = (int64_t)pair_keys.size();
-      hipLaunchKernelGGL(k_level_round, dim3((uint32_t)grid_for(L.n_front)), dim3(kBlock),
-                         0, ctx->stream, L);
-      unsigned long long nn = 0;
-      MGX_HIP_TRY(hipMemcpyAsync(&nn, d_nn, 8, hipMemcpyDeviceToHost, ctx->stream));
-      MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-      front.assign(nn, 0);
-      if (nn > 0) {
-        MGX_HIP_TRY(hipMemcpyAsync(front.data(), d_next, nn * 4, hipMemcpyDeviceToHost,
+      MGX_HIP_TRY(hipMemcpyAsync(d_cnt, pair_cnt.data(), pair_cnt.size() * 4,
+                                 hipMemcpyHostToDevice, ctx->stream));
+    }
+
+    // edge term slot arrays
+    std::vector<int32_t> new_ws, new_vs, del_ws, del_vs;
+    for (int64_t i = 0; i < n_ce; ++i) {
+      auto w = g_k.mg2slot.find(created_e[2 * i]);
+      auto v = g_k.mg2slot.find(created_e[2 * i + 1]);
+      if (w == g_k.mg2slot.end() || v == g_k.mg2slot.end()) continue;
+      new_ws.push_back(w->second);
+      new_vs.push_back(v->second);
+    }
+    for (int64_t i = 0; i < n_de; ++i) {
+      auto w = g_k.mg2slot.find(deleted_e[2 * i]);
+      auto v = g_k.mg2slot.find(deleted_e[2 * i + 1]);
+      if (w == g_k.mg2slot.end() || v == g_k.mg2slot.end()) continue;
+      del_ws.push_back(w->second);
+      del_vs.push_back(v->second);
+    }
+    auto upload_i32 = [&](mgx_scope &own, const std::vector<int32_t> &v,
+                          int32_t **d) -> mgx_status {
+      MGX_TRY(own.alloc_plain(d, (int64_t)v.size()));
+      if (!v.empty())
+        MGX_HIP_TRY(hipMemcpyAsync(*d, v.data(), v.size() * 4, hipMemcpyHostToDevice,
                                    ctx->stream));
-        MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
+      return MGX_OK;
+    };
+    int32_t *d_new_ws = nullptr, *d_new_vs = nullptr, *d_del_ws = nullptr,
+            *d_del_vs = nullptr;
+    MGX_TRY(upload_i32(bufs, new_ws, &d_new_ws));
+    MGX_TRY(upload_i32(bufs, new_vs, &d_new_vs));
+    MGX_TRY(upload_i32(bufs, del_ws, &d_del_ws));
+    MGX_TRY(upload_i32(bufs, del_vs, &d_del_vs));
+
+    // context_new omegas: new_omega[0] = 1 for all current nodes; levels
+    // 1..iteration computed below. Keep as separate device arrays.
+    std::vector<double *> new_omega(g_k.iteration + 1, nullptr);
+    for (int64_t i = 0; i <= g_k.iteration; ++i)
+      MGX_TRY(bufs.alloc_plain(&new_omega[i], g_k.slots_cap));
+    hipLaunchKernelGGL(mgx_k_fill<double>, dim3((uint32_t)grid_for(g_k.slots_cap)),
+                       dim3(kBlock), 0, ctx->stream, g_k.slots_cap, 1.0, new_omega[0]);
+
+    // updated/frontier state in dense space
+    uint32_t *d_updated = nullptr;
+    int32_t *d_front = nullptr, *d_next = nullptr;
+    unsigned long long *d_nn = nullptr;
+    MGX_TRY(bufs.alloc_plain(&d_updated, V));
+    MGX_TRY(bufs.alloc_plain(&d_front, V));
+    MGX_TRY(bufs.alloc_plain(&d_next, V));
+    MGX_TRY(bufs.alloc_plain(&d_nn, 1));
+    std::vector<uint32_t> upd_h(V, 0);
+    std::vector<int32_t> front_h;
+    for (auto mg : updated_mg) {
+      auto it = mg2dense.find(mg);
+      if (it == mg2dense.end()) continue;  // deleted endpoint: not a graph node
+      if (!upd_h[it->second]) {
+        upd_h[it->second] = 1;
+        front_h.push_back(it->second);
       }
     }
-    // next level's initial front/updated = the closure so far
+
+    for (int64_t lvl = 1; lvl <= g_k.iteration; ++lvl) {
+      // new_omega[lvl] = old omega[lvl] (:266-268; only current slots matter)
+      MGX_HIP_TRY(hipMemcpyAsync(new_omega[lvl], g_k.omega[lvl], g_k.slots_cap * 8,
+                                 hipMemcpyDeviceToDevice, ctx->stream));
+      MGX_HIP_TRY(hipMemcpyAsync(d_updated, upd_h.data(), V * 4,
+                                 hipMemcpyHostToDevice, ctx->stream));
+      // frontier rounds: every updated node processes its out-edges exactly
+      // once per level; nodes marked mid-level join later rounds
+      std::vector<int32_t> front = front_h;
+      MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
+      while (!front.empty()) {
+        MGX_HIP_TRY(hipMemcpyAsync(d_front, front.data(), front.size() * 4,
+                                   hipMemcpyHostToDevice, ctx->stream));
+        MGX_HIP_TRY(hipMemsetAsync(d_nn, 0, 8, ctx->stream));
+        LevelArgs L;
+        L.front = d_front;
+        L.n_front = (int64_t)front.size();
+        L.out_row_ptr = g->out_row_ptr;
+        L.out_col = g->out_col;
+        L.dense2slot = m.dense2slot;
+        L.omega_new_prev = new_omega[lvl - 1];
+        L.omega_old_prev = g_k.omega[lvl - 1];
+        L.omega_new_cur = new_omega[lvl];
+        L.updated = d_updated;
+        L.next = d_next;
+        L.n_next = d_nn;
+        L.new_pairs = d_pairs;
+        L.new_cnt = d_cnt;
+        L.n_new_pairs = (int64_t)pair_keys.size();
+        hipLaunchKernelGGL(k_level_round, dim3((uint32_t)grid_for(L.n_front)), dim3(kBlock),
+                           0, ctx->stream, L);
+        unsigned long long nn = 0;
+        MGX_HIP_TRY(hipMemcpyAsync(&nn, d_nn, 8, hipMemcpyDeviceToHost, ctx->stream));
+        MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        front.assign(nn, 0);
+        if (nn > 0) {
+          MGX_HIP_TRY(hipMemcpyAsync(front.data(), d_next, nn * 4, hipMemcpyDeviceToHost,
+                                     ctx->stream));
+          MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        }
+      }
+      // next level's initial front/updated = the closure so far
+      {
+        std::vector<uint32_t> cur(V);
+        MGX_HIP_TRY(hipMemcpyAsync(cur.data(), d_updated, V * 4,
+                                   hipMemcpyDeviceToHost, ctx->stream));
+        MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        upd_h = cur;
+        front_h.clear();
+        for (int64_t v = 0; v < V; ++v)
+          if (upd_h[v]) front_h.push_back((int32_t)v);
+      }
+      // edge terms (:294-301)
+      if (!new_ws.empty() || !del_ws.empty()) {
+        hipLaunchKernelGGL(k_edge_terms,
+                           dim3((uint32_t)grid_for((int64_t)(new_ws.size() + del_ws.size()))),
+                           dim3(kBlock), 0, ctx->stream, (int64_t)new_ws.size(), d_new_ws,
+                           d_new_vs, (int64_t)del_ws.size(), d_del_ws, d_del_vs,
+                           new_omega[lvl - 1], g_k.omega[lvl - 1], new_omega[lvl]);
+      }
+      // centralities for the updated set (:304-312)
+      std::vector<int32_t> upd_slots;
+      for (auto v : front_h) upd_slots.push_back(m.d2s_h[v]);
+      mgx_scope slot_bufs(ctx);
+      int32_t *d_upd_slots = nullptr;
+      MGX_TRY(upload_i32(slot_bufs, upd_slots, &d_upd_slots));
+      hipLaunchKernelGGL(k_cent_level, dim3((uint32_t)grid_for((int64_t)upd_slots.size())),
+                         dim3(kBlock), 0, ctx->stream, (int64_t)upd_slots.size(),
+                         d_upd_slots, lvl, pow(g_k.alpha, (double)lvl), new_omega[lvl],
+                         g_k.omega[lvl], g_k.cent[lvl - 1], g_k.cent[lvl]);
+      MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+
+    // merge new omegas into state (:427-431)
+    for (int64_t lvl = 1; lvl <= g_k.iteration; ++lvl) {
+      MGX_HIP_TRY(hipMemcpyAsync(g_k.omega[lvl], new_omega[lvl], g_k.slots_cap * 8,
+                                 hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
+
+    // lr/ur refresh for updated nodes (:434-440; no gamma)
     {
-      std::vector<uint32_t> cur(V);
-      MGX_HIP_TRY(hipMemcpyAsync(cur.data(), d_updated, V * 4,
+      std::vector<int32_t> upd_slots;
+      for (auto v : front_h) upd_slots.push_back(m.d2s_h[v]);
+      mgx_scope slot_bufs(ctx);
+      int32_t *d_upd_slots = nullptr;
+      MGX_TRY(upload_i32(slot_bufs, upd_slots, &d_upd_slots));
+      hipLaunchKernelGGL(k_bounds_refresh,
+                         dim3((uint32_t)grid_for((int64_t)upd_slots.size())), dim3(kBlock),
+                         0, ctx->stream, (int64_t)upd_slots.size(), d_upd_slots,
+                         g_k.cent[g_k.iteration], g_k.omega[g_k.iteration],
+                         pow(g_k.alpha, (double)(g_k.iteration + 1)), g_k.lr, g_k.ur);
+      MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+
+    // re-activation (:442-455): min lr over active, then ur >= min_lr - eps
+    {
+      std::vector<double> lr_h(g_k.slots_cap), ur_h(g_k.slots_cap);
+      MGX_HIP_TRY(hipMemcpyAsync(lr_h.data(), g_k.lr, g_k.slots_cap * 8,
+                                 hipMemcpyDeviceToHost, ctx->stream));
+      MGX_HIP_TRY(hipMemcpyAsync(ur_h.data(), g_k.ur, g_k.slots_cap * 8,
                                  hipMemcpyDeviceToHost, ctx->stream));
       MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-      upd_h = cur;
-      front_h.clear();
-      for (int64_t v = 0; v < V; ++v)
-        if (upd_h[v]) front_h.push_back((int32_t)v);
+      double min_lr = 1e300;
+      for (size_t s = 0; s < g_k.active_h.size(); ++s)
+        if (g_k.active_h[s] && lr_h[s] < min_lr) min_lr = lr_h[s];
+      for (int64_t v = 0; v < V; ++v) {
+        const int32_t s = m.d2s_h[v];
+        if (ur_h[s] >= (min_lr - g_k.eps)) g_k.active_h[s] = 1;
+      }
     }
-    // edge terms (:294-301)
-    if (!new_ws.empty() || !del_ws.empty()) {
-      hipLaunchKernelGGL(k_edge_terms,
-                         dim3((uint32_t)grid_for((int64_t)(new_ws.size() + del_ws.size()))),
-                         dim3(kBlock), 0, ctx->stream, (int64_t)new_ws.size(), d_new_ws,
-                         d_new_vs, (int64_t)del_ws.size(), d_del_ws, d_del_vs,
-                         new_omega[lvl - 1], g_k.omega[lvl - 1], new_omega[lvl]);
-    }
-    // centralities for the updated set (:304-312)
-    std::vector<int32_t> upd_slots;
-    for (auto v : front_h) upd_slots.push_back(m.d2s_h[v]);
-    int32_t *d_upd_slots = nullptr;
-    MGX_TRY(upload_i32(upd_slots, &d_upd_slots));
-    hipLaunchKernelGGL(k_cent_level, dim3((uint32_t)grid_for((int64_t)upd_slots.size())),
-                       dim3(kBlock), 0, ctx->stream, (int64_t)upd_slots.size(),
-                       d_upd_slots, lvl, pow(g_k.alpha, (double)lvl), new_omega[lvl],
-                       g_k.omega[lvl], g_k.cent[lvl - 1], g_k.cent[lvl]);
-    MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    (void)hipFree(d_upd_slots);
-  }
-
-  // merge new omegas into state (:427-431)
-  for (int64_t lvl = 1; lvl <= g_k.iteration; ++lvl) {
-    MGX_HIP_TRY(hipMemcpyAsync(g_k.omega[lvl], new_omega[lvl], g_k.slots_cap * 8,
-                               hipMemcpyDeviceToDevice, ctx->stream));
-  }
-  MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  cleanup_new();
-
-  // lr/ur refresh for updated nodes (:434-440; no gamma)
-  {
-    std::vector<int32_t> upd_slots;
-    for (auto v : front_h) upd_slots.push_back(m.d2s_h[v]);
-    int32_t *d_upd_slots = nullptr;
-    MGX_TRY(upload_i32(upd_slots, &d_upd_slots));
-    hipLaunchKernelGGL(k_bounds_refresh,
-                       dim3((uint32_t)grid_for((int64_t)upd_slots.size())), dim3(kBlock),
-                       0, ctx->stream, (int64_t)upd_slots.size(), d_upd_slots,
-                       g_k.cent[g_k.iteration], g_k.omega[g_k.iteration],
-                       pow(g_k.alpha, (double)(g_k.iteration + 1)), g_k.lr, g_k.ur);
-    MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    (void)hipFree(d_upd_slots);
-  }
-
-  // re-activation (:442-455): min lr over active, then ur >= min_lr - eps
-  {
-    std::vector<double> lr_h(g_k.slots_cap), ur_h(g_k.slots_cap);
-    MGX_HIP_TRY(hipMemcpyAsync(lr_h.data(), g_k.lr, g_k.slots_cap * 8,
-                               hipMemcpyDeviceToHost, ctx->stream));
-    MGX_HIP_TRY(hipMemcpyAsync(ur_h.data(), g_k.ur, g_k.slots_cap * 8,
-                               hipMemcpyDeviceToHost, ctx->stream));
-    MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    double min_lr = 1e300;
-    for (size_t s = 0; s < g_k.active_h.size(); ++s)
-      if (g_k.active_h[s] && lr_h[s] < min_lr) min_lr = lr_h[s];
-    for (int64_t v = 0; v < V; ++v) {
-      const int32_t s = m.d2s_h[v];
-      if (ur_h[s] >= (min_lr - g_k.eps)) g_k.active_h[s] = 1;
+    // deleted vertices (:458-464)
+    for (int64_t i = 0; i < n_dv; ++i) {
+      auto it = g_k.mg2slot.find(deleted_v[i]);
+      if (it == g_k.mg2slot.end()) continue;
+      g_k.alive_h[it->second] = 0;
+      g_k.active_h[it->second] = 0;
     }
   }
-  // deleted vertices (:458-464)
-  for (int64_t i = 0; i < n_dv; ++i) {
-    auto it = g_k.mg2slot.find(deleted_v[i]);
-    if (it == g_k.mg2slot.end()) continue;
-    g_k.alive_h[it->second] = 0;
-    g_k.active_h[it->second] = 0;
-  }
-
-  (void)hipFree(d_pairs);
-  (void)hipFree(d_cnt);
-  (void)hipFree(d_new_ws);
-  (void)hipFree(d_new_vs);
-  (void)hipFree(d_del_ws);
-  (void)hipFree(d_del_vs);
-  (void)hipFree(d_updated);
-  (void)hipFree(d_front);
-  (void)hipFree(d_next);
-  (void)hipFree(d_nn);
 
   MGX_TRY(kon_loop(ctx, g, m, gamma));
   return kon_output(ctx, m, out);

@@ -406,10 +406,11 @@ mgx_status lrt_grow_slots(mgx_context *ctx, int64_t need) {
   uint64_t *noff = nullptr;
   uint32_t *nlen = nullptr, *ntu = nullptr;
   double *nsw = nullptr;
-  MGX_HIP_TRY(mgx_hip_malloc(&noff, cap * 8));
-  MGX_HIP_TRY(mgx_hip_malloc(&nlen, cap * 4));
-  MGX_HIP_TRY(mgx_hip_malloc(&ntu, cap * 4));
-  MGX_HIP_TRY(mgx_hip_malloc(&nsw, cap * 8));
+  mgx_scope grown(ctx);
+  MGX_TRY(grown.alloc_plain(&noff, cap));
+  MGX_TRY(grown.alloc_plain(&nlen, cap));
+  MGX_TRY(grown.alloc_plain(&ntu, cap));
+  MGX_TRY(grown.alloc_plain(&nsw, cap));
   MGX_HIP_TRY(hipMemsetAsync(nlen, 0, cap * 4, ctx->stream));
   MGX_HIP_TRY(hipMemsetAsync(ntu, 0, cap * 4, ctx->stream));
   MGX_HIP_TRY(hipMemsetAsync(noff, 0, cap * 8, ctx->stream));
@@ -428,10 +429,10 @@ mgx_status lrt_grow_slots(mgx_context *ctx, int64_t need) {
   if (g_l.len) (void)hipFree(g_l.len);
   if (g_l.times_upd) (void)hipFree(g_l.times_upd);
   if (g_l.sum_w) (void)hipFree(g_l.sum_w);
-  g_l.off = noff;
-  g_l.len = nlen;
-  g_l.times_upd = ntu;
-  g_l.sum_w = nsw;
+  g_l.off = grown.give_up(noff);
+  g_l.len = grown.give_up(nlen);
+  g_l.times_upd = grown.give_up(ntu);
+  g_l.sum_w = grown.give_up(nsw);
   g_l.slots_cap = cap;
   return MGX_OK;
 }
@@ -489,8 +490,9 @@ mgx_status lrt_set_structures(mgx_context *ctx, mgx_graph *g, const LrtMaps &m,
   if (n == 0) return MGX_OK;
   int32_t *d_nodes = nullptr;
   uint32_t *d_counts = nullptr;
-  MGX_HIP_TRY(mgx_hip_malloc(&d_nodes, n * 4));
-  MGX_HIP_TRY(mgx_hip_malloc(&d_counts, n * 4));
+  mgx_scope bufs(ctx);
+  MGX_TRY(bufs.alloc_plain(&d_nodes, n));
+  MGX_TRY(bufs.alloc_plain(&d_counts, n));
   MGX_HIP_TRY(hipMemcpyAsync(d_nodes, nodes_dense.data(), n * 4, hipMemcpyHostToDevice,
                              ctx->stream));
   hipLaunchKernelGGL(k_set_count, dim3((uint32_t)grid_for(n)), dim3(kBlock), 0,
@@ -505,8 +507,9 @@ mgx_status lrt_set_structures(mgx_context *ctx, mgx_graph *g, const LrtMaps &m,
     while (cap < need) cap *= 2;
     int32_t *nl = nullptr;
     double *np = nullptr;
-    MGX_HIP_TRY(mgx_hip_malloc(&nl, cap * 4));
-    MGX_HIP_TRY(mgx_hip_malloc(&np, cap * 8));
+    mgx_scope grown(ctx);
+    MGX_TRY(grown.alloc_plain(&nl, cap));
+    MGX_TRY(grown.alloc_plain(&np, cap));
     if (g_l.pool_used > 0) {
       MGX_HIP_TRY(hipMemcpyAsync(nl, g_l.lab, g_l.pool_used * 4,
                                  hipMemcpyDeviceToDevice, ctx->stream));
@@ -516,13 +519,13 @@ mgx_status lrt_set_structures(mgx_context *ctx, mgx_graph *g, const LrtMaps &m,
     MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (g_l.lab) (void)hipFree(g_l.lab);
     if (g_l.p) (void)hipFree(g_l.p);
-    g_l.lab = nl;
-    g_l.p = np;
+    g_l.lab = grown.give_up(nl);
+    g_l.p = grown.give_up(np);
     g_l.pool_cap = cap;
   }
   for (auto &o : seg_off) o += (uint64_t)g_l.pool_used;
   uint64_t *d_seg = nullptr;
-  MGX_HIP_TRY(mgx_hip_malloc(&d_seg, n * 8));
+  MGX_TRY(bufs.alloc_plain(&d_seg, n));
   MGX_HIP_TRY(hipMemcpyAsync(d_seg, seg_off.data(), n * 8, hipMemcpyHostToDevice,
                              ctx->stream));
   SetArgs A;
@@ -544,9 +547,6 @@ mgx_status lrt_set_structures(mgx_context *ctx, mgx_graph *g, const LrtMaps &m,
                      A);
   MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
   g_l.pool_used += (int64_t)total;
-  (void)hipFree(d_nodes);
-  (void)hipFree(d_counts);
-  (void)hipFree(d_seg);
   return MGX_OK;
 }
 
@@ -564,9 +564,10 @@ mgx_status lrt_iteration(mgx_context *ctx, const LrtMaps &m, const uint32_t *row
   int32_t *d_nodes = nullptr;
   uint8_t *d_sel = nullptr;
   uint32_t *d_bound = nullptr;
-  MGX_HIP_TRY(mgx_hip_malloc(&d_nodes, n * 4));
-  MGX_HIP_TRY(mgx_hip_malloc(&d_sel, n));
-  MGX_HIP_TRY(mgx_hip_malloc(&d_bound, n * 4));
+  mgx_scope bufs(ctx);
+  MGX_TRY(bufs.alloc_plain(&d_nodes, n));
+  MGX_TRY(bufs.alloc_plain(&d_sel, n));
+  MGX_TRY(bufs.alloc_plain(&d_bound, n));
   MGX_HIP_TRY(hipMemcpyAsync(d_nodes, candidates.data(), n * 4, hipMemcpyHostToDevice,
                              ctx->stream));
   hipLaunchKernelGGL(k_distinct, dim3((uint32_t)grid_for(n)), dim3(kBlock), 0, ctx->stream,
@@ -595,10 +596,10 @@ mgx_status lrt_iteration(mgx_context *ctx, const LrtMaps &m, const uint32_t *row
   double *scr_p = nullptr;
   uint64_t *d_scr_off = nullptr;
   uint32_t *d_cnt = nullptr;
-  MGX_HIP_TRY(mgx_hip_malloc(&scr_lab, (scr_total > 0 ? scr_total : 1) * 4));
-  MGX_HIP_TRY(mgx_hip_malloc(&scr_p, (scr_total > 0 ? scr_total : 1) * 8));
-  MGX_HIP_TRY(mgx_hip_malloc(&d_scr_off, n * 8));
-  MGX_HIP_TRY(mgx_hip_malloc(&d_cnt, n * 4));
+  MGX_TRY(bufs.alloc_plain(&scr_lab, (int64_t)scr_total));
+  MGX_TRY(bufs.alloc_plain(&scr_p, (int64_t)scr_total));
+  MGX_TRY(bufs.alloc_plain(&d_scr_off, n));
+  MGX_TRY(bufs.alloc_plain(&d_cnt, n));
   MGX_HIP_TRY(hipMemcpyAsync(d_scr_off, scr_off.data(), n * 8, hipMemcpyHostToDevice,
                              ctx->stream));
   PropArgs P;
@@ -639,16 +640,7 @@ mgx_status lrt_iteration(mgx_context *ctx, const LrtMaps &m, const uint32_t *row
     }
   }
   *none_updated = !any;
-  if (!any) {
-    (void)hipFree(d_nodes);
-    (void)hipFree(d_sel);
-    (void)hipFree(d_bound);
-    (void)hipFree(scr_lab);
-    (void)hipFree(scr_p);
-    (void)hipFree(d_scr_off);
-    (void)hipFree(d_cnt);
-    return MGX_OK;
-  }
+  if (!any) return MGX_OK;
 
   // new pool = sum over slots of new lens
   std::vector<uint32_t> old_len(n_slots);
@@ -669,14 +661,14 @@ mgx_status lrt_iteration(mgx_context *ctx, const LrtMaps &m, const uint32_t *row
   uint32_t *d_out_len = nullptr;
   unsigned long long *d_most = nullptr;
   uint32_t *d_any = nullptr;
-  MGX_HIP_TRY(mgx_hip_malloc(&nlab, (total > 0 ? total : 1) * 4));
-  MGX_HIP_TRY(mgx_hip_malloc(&np, (total > 0 ? total : 1) * 8));
-  MGX_HIP_TRY(mgx_hip_malloc(&d_new_off, n_slots * 8));
-  MGX_HIP_TRY(mgx_hip_malloc(&d_slot_sel, n_slots * 4));
-  MGX_HIP_TRY(mgx_hip_malloc(&d_out_off, n_slots * 8));
-  MGX_HIP_TRY(mgx_hip_malloc(&d_out_len, n_slots * 4));
-  MGX_HIP_TRY(mgx_hip_malloc(&d_most, 8));
-  MGX_HIP_TRY(mgx_hip_malloc(&d_any, 4));
+  MGX_TRY(bufs.alloc_plain(&nlab, (int64_t)total));
+  MGX_TRY(bufs.alloc_plain(&np, (int64_t)total));
+  MGX_TRY(bufs.alloc_plain(&d_new_off, n_slots));
+  MGX_TRY(bufs.alloc_plain(&d_slot_sel, n_slots));
+  MGX_TRY(bufs.alloc_plain(&d_out_off, n_slots));
+  MGX_TRY(bufs.alloc_plain(&d_out_len, n_slots));
+  MGX_TRY(bufs.alloc_plain(&d_most, 1));
+  MGX_TRY(bufs.alloc_plain(&d_any, 1));
   MGX_HIP_TRY(hipMemcpyAsync(d_new_off, new_off.data(), n_slots * 8,
                              hipMemcpyHostToDevice, ctx->stream));
   MGX_HIP_TRY(hipMemcpyAsync(d_slot_sel, slot_sel.data(), n_slots * 4,
@@ -714,25 +706,11 @@ mgx_status lrt_iteration(mgx_context *ctx, const LrtMaps &m, const uint32_t *row
   MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
   (void)hipFree(g_l.lab);
   (void)hipFree(g_l.p);
-  g_l.lab = nlab;
-  g_l.p = np;
+  g_l.lab = bufs.give_up(nlab);
+  g_l.p = bufs.give_up(np);
   g_l.pool_used = (int64_t)total;
   g_l.pool_cap = (int64_t)(total > 0 ? total : 1);
   *most_updates = most;
-
-  (void)hipFree(d_nodes);
-  (void)hipFree(d_sel);
-  (void)hipFree(d_bound);
-  (void)hipFree(scr_lab);
-  (void)hipFree(scr_p);
-  (void)hipFree(d_scr_off);
-  (void)hipFree(d_cnt);
-  (void)hipFree(d_new_off);
-  (void)hipFree(d_slot_sel);
-  (void)hipFree(d_out_off);
-  (void)hipFree(d_out_len);
-  (void)hipFree(d_most);
-  (void)hipFree(d_any);
   return MGX_OK;
 }
 
@@ -740,20 +718,21 @@ mgx_status lrt_iteration(mgx_context *ctx, const LrtMaps &m, const uint32_t *row
 mgx_status lrt_all_labels(mgx_context *ctx, const LrtMaps &m, int64_t *out_label) {
   const int64_t n_slots = (int64_t)g_l.slot2mg.size();
   if (n_slots == 0 || m.V == 0) return MGX_OK;
-  int64_t *d_s2mg = nullptr, *d_raw = nullptr;
-  MGX_HIP_TRY(mgx_hip_malloc(&d_s2mg, n_slots * 8));
-  MGX_HIP_TRY(mgx_hip_malloc(&d_raw, n_slots * 8));
-  MGX_HIP_TRY(hipMemcpyAsync(d_s2mg, g_l.slot2mg.data(), n_slots * 8,
-                             hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(k_argmax, dim3((uint32_t)grid_for(n_slots)), dim3(kBlock), 0,
-                     ctx->stream, n_slots, g_l.lab, g_l.p, g_l.off, g_l.len, d_s2mg,
-                     d_raw);
   std::vector<int64_t> raw(n_slots);
-  MGX_HIP_TRY(hipMemcpyAsync(raw.data(), d_raw, n_slots * 8, hipMemcpyDeviceToHost,
-                             ctx->stream));
-  MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  (void)hipFree(d_s2mg);
-  (void)hipFree(d_raw);
+  {
+    mgx_scope bufs(ctx);
+    int64_t *d_s2mg = nullptr, *d_raw = nullptr;
+    MGX_TRY(bufs.alloc_plain(&d_s2mg, n_slots));
+    MGX_TRY(bufs.alloc_plain(&d_raw, n_slots));
+    MGX_HIP_TRY(hipMemcpyAsync(d_s2mg, g_l.slot2mg.data(), n_slots * 8,
+                               hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_argmax, dim3((uint32_t)grid_for(n_slots)), dim3(kBlock), 0,
+                       ctx->stream, n_slots, g_l.lab, g_l.p, g_l.off, g_l.len, d_s2mg,
+                       d_raw);
+    MGX_HIP_TRY(hipMemcpyAsync(raw.data(), d_raw, n_slots * 8, hipMemcpyDeviceToHost,
+                               ctx->stream));
+    MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  }
   // renumber in ascending label-mg-id order (:135-141); only ALIVE slots
   std::set<int64_t> ordered;
   for (int64_t s = 0; s < n_slots; ++s)

@@ -80,11 +80,20 @@ struct Level {
   int64_t ne2 = 0;
 };
 
-void free_level(Level *L) {
-  if (L->row_ptr) (void)hipFree(L->row_ptr);
-  if (L->col) (void)hipFree(L->col);
-  if (L->w) (void)hipFree(L->w);
-  if (L->node_w) (void)hipFree(L->node_w);
+// The four arrays of L (nv and ne2 set) in the scope that owns the level.
+mgx_status alloc_level(mgx_scope &own, Level *L) {
+  MGX_TRY(own.alloc_plain(&L->row_ptr, L->nv + 1));
+  MGX_TRY(own.alloc_plain(&L->col, L->ne2));
+  MGX_TRY(own.alloc_plain(&L->w, L->ne2));
+  MGX_TRY(own.alloc_plain(&L->node_w, L->nv));
+  return MGX_OK;
+}
+
+void free_level(mgx_scope &own, Level *L) {
+  own.release(L->row_ptr);
+  own.release(L->col);
+  own.release(L->w);
+  own.release(L->node_w);
   *L = Level{};
 }
 
@@ -509,13 +518,12 @@ extern "C" mgx_status mgx_leiden(mgx_context *ctx, mgx_graph *g, double gamma,
   // added once (c >= v).
   const double gamma_n = gamma / sum_of_weights;
 
+  // Owns the current level's arrays and its partition (d_comm, d_csize).
+  mgx_scope own(ctx);
   Level L;
   L.nv = V;
   L.ne2 = (int64_t)col2.size();
-  MGX_HIP_TRY(mgx_hip_malloc(&L.row_ptr, (V + 1) * 4));
-  MGX_HIP_TRY(mgx_hip_malloc(&L.col, (L.ne2 > 0 ? L.ne2 : 1) * 4));
-  MGX_HIP_TRY(mgx_hip_malloc(&L.w, (L.ne2 > 0 ? L.ne2 : 1) * 8));
-  MGX_HIP_TRY(mgx_hip_malloc(&L.node_w, V * 8));
+  MGX_TRY(alloc_level(own, &L));
   MGX_HIP_TRY(hipMemcpyAsync(L.row_ptr, rp2.data(), (V + 1) * 4, hipMemcpyHostToDevice,
                              ctx->stream));
   if (L.ne2 > 0) {
@@ -541,8 +549,8 @@ extern "C" mgx_status mgx_leiden(mgx_context *ctx, mgx_graph *g, double gamma,
   // it; at level 0 it is singleton.
   int32_t *d_comm = nullptr;
   uint32_t *d_csize = nullptr;
-  MGX_HIP_TRY(mgx_hip_malloc(&d_comm, V * 4));
-  MGX_HIP_TRY(mgx_hip_malloc(&d_csize, V * 4));
+  MGX_TRY(own.alloc_plain(&d_comm, V));
+  MGX_TRY(own.alloc_plain(&d_csize, V));
   hipLaunchKernelGGL(mgx_k_iota<int32_t>, dim3((uint32_t)grid_for(V)), dim3(kBlock), 0,
                      ctx->stream, V, d_comm);
   hipLaunchKernelGGL(mgx_k_fill<uint32_t>, dim3((uint32_t)grid_for(V)), dim3(kBlock), 0,
@@ -582,13 +590,14 @@ extern "C" mgx_status mgx_leiden(mgx_context *ctx, mgx_graph *g, double gamma,
     int32_t *d_pkeys = nullptr;
     double *d_pvals = nullptr;
     unsigned long long *d_cnt = nullptr;
-    MGX_HIP_TRY(mgx_hip_malloc(&d_srows, (srows.empty() ? 1 : srows.size()) * 4));
-    MGX_HIP_TRY(mgx_hip_malloc(&d_brows, (brows.empty() ? 1 : brows.size()) * 4));
-    MGX_HIP_TRY(mgx_hip_malloc(&d_target, nv * 4));
-    MGX_HIP_TRY(mgx_hip_malloc(&d_poff, caps.size() * 8));
-    MGX_HIP_TRY(mgx_hip_malloc(&d_pkeys, (pool_total ? pool_total : 1) * 4));
-    MGX_HIP_TRY(mgx_hip_malloc(&d_pvals, (pool_total ? pool_total : 1) * 8));
-    MGX_HIP_TRY(mgx_hip_malloc(&d_cnt, 8));
+    mgx_scope level_bufs(ctx);
+    MGX_TRY(level_bufs.alloc_plain(&d_srows, (int64_t)srows.size()));
+    MGX_TRY(level_bufs.alloc_plain(&d_brows, (int64_t)brows.size()));
+    MGX_TRY(level_bufs.alloc_plain(&d_target, nv));
+    MGX_TRY(level_bufs.alloc_plain(&d_poff, (int64_t)caps.size()));
+    MGX_TRY(level_bufs.alloc_plain(&d_pkeys, (int64_t)pool_total));
+    MGX_TRY(level_bufs.alloc_plain(&d_pvals, (int64_t)pool_total));
+    MGX_TRY(level_bufs.alloc_plain(&d_cnt, 1));
     if (!srows.empty())
       MGX_HIP_TRY(hipMemcpyAsync(d_srows, srows.data(), srows.size() * 4,
                                  hipMemcpyHostToDevice, ctx->stream));
@@ -600,8 +609,9 @@ extern "C" mgx_status mgx_leiden(mgx_context *ctx, mgx_graph *g, double gamma,
 
     unsigned long long empties_before = 0;
     {
+      mgx_scope count_bufs(ctx);
       unsigned long long *d_t = nullptr;
-      MGX_HIP_TRY(mgx_hip_malloc(&d_t, 16));
+      MGX_TRY(count_bufs.alloc_plain(&d_t, 2));
       MGX_HIP_TRY(hipMemsetAsync(d_t, 0, 16, ctx->stream));
       hipLaunchKernelGGL(k_count_nonsingleton, dim3((uint32_t)grid_for(nv)), dim3(kBlock),
                          0, ctx->stream, nv, d_csize, d_t, d_t + 1);
@@ -609,7 +619,6 @@ extern "C" mgx_status mgx_leiden(mgx_context *ctx, mgx_graph *g, double gamma,
       MGX_HIP_TRY(hipMemcpyAsync(h_t, d_t, 16, hipMemcpyDeviceToHost, ctx->stream));
       MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
       empties_before = (unsigned long long)nv - h_t[1];
-      (void)hipFree(d_t);
     }
 
     MoveArgs M;
@@ -680,8 +689,9 @@ extern "C" mgx_status mgx_leiden(mgx_context *ctx, mgx_graph *g, double gamma,
     // singleton / empties accounting
     unsigned long long nonsingleton = 0, nonempty = 0;
     {
+      mgx_scope count_bufs(ctx);
       unsigned long long *d_t = nullptr;
-      MGX_HIP_TRY(mgx_hip_malloc(&d_t, 16));
+      MGX_TRY(count_bufs.alloc_plain(&d_t, 2));
       MGX_HIP_TRY(hipMemsetAsync(d_t, 0, 16, ctx->stream));
       hipLaunchKernelGGL(k_count_nonsingleton, dim3((uint32_t)grid_for(nv)), dim3(kBlock),
                          0, ctx->stream, nv, d_csize, d_t, d_t + 1);
@@ -690,7 +700,6 @@ extern "C" mgx_status mgx_leiden(mgx_context *ctx, mgx_graph *g, double gamma,
       MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
       nonsingleton = h_t[0];
       nonempty = h_t[1];
-      (void)hipFree(d_t);
     }
     const unsigned long long move_empties =
         ((unsigned long long)nv - nonempty) - empties_before;
@@ -718,69 +727,62 @@ extern "C" mgx_status mgx_leiden(mgx_context *ctx, mgx_graph *g, double gamma,
       }
       std::vector<int32_t> locidx(nv);
       for (int64_t i = 0; i < nv; ++i) locidx[members[i]] = 0;  // filled in kernel
-      int32_t *d_members = nullptr, *d_locidx = nullptr, *d_rcomm = nullptr;
-      uint32_t *d_memoff = nullptr, *d_rsize = nullptr;
-      double *d_extw = nullptr, *d_edgew = nullptr, *d_prob = nullptr;
-      int32_t *d_nbc = nullptr, *d_cslot = nullptr;
-      MGX_HIP_TRY(mgx_hip_malloc(&d_members, nv * 4));
-      MGX_HIP_TRY(mgx_hip_malloc(&d_locidx, nv * 4));
-      MGX_HIP_TRY(mgx_hip_malloc(&d_rcomm, nv * 4));
-      MGX_HIP_TRY(mgx_hip_malloc(&d_memoff, (nv + 1) * 4));
-      MGX_HIP_TRY(mgx_hip_malloc(&d_rsize, nv * 4));
-      MGX_HIP_TRY(mgx_hip_malloc(&d_extw, nv * 8));
-      MGX_HIP_TRY(mgx_hip_malloc(&d_edgew, nv * 8));
-      MGX_HIP_TRY(mgx_hip_malloc(&d_prob, nv * 8));
-      MGX_HIP_TRY(mgx_hip_malloc(&d_nbc, nv * 4));
-      MGX_HIP_TRY(mgx_hip_malloc(&d_cslot, nv * 4));
-      MGX_HIP_TRY(hipMemcpyAsync(d_members, members.data(), nv * 4,
-                                 hipMemcpyHostToDevice, ctx->stream));
-      MGX_HIP_TRY(hipMemcpyAsync(d_memoff, mem_off.data(), (nv + 1) * 4,
-                                 hipMemcpyHostToDevice, ctx->stream));
-      // rcomm starts singleton-local: filled per subset inside k_refine
-      hipLaunchKernelGGL(mgx_k_fill<int32_t>, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0,
-                         ctx->stream, nv, 0, d_rcomm);
-      MGX_HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, ctx->stream));
-      RefineArgs R;
-      R.row_ptr = L.row_ptr;
-      R.col = L.col;
-      R.w = L.w;
-      R.node_w = L.node_w;
-      R.comm = d_comm;
-      R.members = d_members;
-      R.mem_off = d_memoff;
-      R.n_comm = nv;
-      R.loc_idx = d_locidx;
-      R.rcomm_loc = d_rcomm;
-      R.ext_w = d_extw;
-      R.edge_w = d_edgew;
-      R.nb_comms = d_nbc;
-      R.nb_slot = d_cslot;
-      R.prob = d_prob;
-      R.rsize = d_rsize;
-      R.gamma = gamma_n;
-      R.theta = theta;
-      R.resolution = resolution;
-      R.seed = mgx_hash64(ms, (uint64_t)level + 1);
-      R.n_merged = d_cnt;
-      MGX_LEIDEN_LOG("  refine launch n_comm=%lld", (long long)nv);
-      hipLaunchKernelGGL(k_refine, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0,
-                         ctx->stream, R);
       unsigned long long merged = 0;
-      MGX_HIP_TRY(hipMemcpyAsync(&merged, d_cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
       std::vector<int32_t> rcomm_h(nv);
-      MGX_HIP_TRY(hipMemcpyAsync(rcomm_h.data(), d_rcomm, nv * 4, hipMemcpyDeviceToHost,
-                                 ctx->stream));
-      MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-      (void)hipFree(d_members);
-      (void)hipFree(d_locidx);
-      (void)hipFree(d_memoff);
-      (void)hipFree(d_rsize);
-      (void)hipFree(d_extw);
-      (void)hipFree(d_edgew);
-      (void)hipFree(d_prob);
-      (void)hipFree(d_nbc);
-      (void)hipFree(d_cslot);
-      (void)hipFree(d_rcomm);
+      {
+        mgx_scope refine_bufs(ctx);
+        int32_t *d_members = nullptr, *d_locidx = nullptr, *d_rcomm = nullptr;
+        uint32_t *d_memoff = nullptr, *d_rsize = nullptr;
+        double *d_extw = nullptr, *d_edgew = nullptr, *d_prob = nullptr;
+        int32_t *d_nbc = nullptr, *d_cslot = nullptr;
+        MGX_TRY(refine_bufs.alloc_plain(&d_members, nv));
+        MGX_TRY(refine_bufs.alloc_plain(&d_locidx, nv));
+        MGX_TRY(refine_bufs.alloc_plain(&d_rcomm, nv));
+        MGX_TRY(refine_bufs.alloc_plain(&d_memoff, nv + 1));
+        MGX_TRY(refine_bufs.alloc_plain(&d_rsize, nv));
+        MGX_TRY(refine_bufs.alloc_plain(&d_extw, nv));
+        MGX_TRY(refine_bufs.alloc_plain(&d_edgew, nv));
+        MGX_TRY(refine_bufs.alloc_plain(&d_prob, nv));
+        MGX_TRY(refine_bufs.alloc_plain(&d_nbc, nv));
+        MGX_TRY(refine_bufs.alloc_plain(&d_cslot, nv));
+        MGX_HIP_TRY(hipMemcpyAsync(d_members, members.data(), nv * 4,
+                                   hipMemcpyHostToDevice, ctx->stream));
+        MGX_HIP_TRY(hipMemcpyAsync(d_memoff, mem_off.data(), (nv + 1) * 4,
+                                   hipMemcpyHostToDevice, ctx->stream));
+        // rcomm starts singleton-local: filled per subset inside k_refine
+        hipLaunchKernelGGL(mgx_k_fill<int32_t>, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0,
+                           ctx->stream, nv, 0, d_rcomm);
+        MGX_HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, ctx->stream));
+        RefineArgs R;
+        R.row_ptr = L.row_ptr;
+        R.col = L.col;
+        R.w = L.w;
+        R.node_w = L.node_w;
+        R.comm = d_comm;
+        R.members = d_members;
+        R.mem_off = d_memoff;
+        R.n_comm = nv;
+        R.loc_idx = d_locidx;
+        R.rcomm_loc = d_rcomm;
+        R.ext_w = d_extw;
+        R.edge_w = d_edgew;
+        R.nb_comms = d_nbc;
+        R.nb_slot = d_cslot;
+        R.prob = d_prob;
+        R.rsize = d_rsize;
+        R.gamma = gamma_n;
+        R.theta = theta;
+        R.resolution = resolution;
+        R.seed = mgx_hash64(ms, (uint64_t)level + 1);
+        R.n_merged = d_cnt;
+        MGX_LEIDEN_LOG("  refine launch n_comm=%lld", (long long)nv);
+        hipLaunchKernelGGL(k_refine, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0,
+                           ctx->stream, R);
+        MGX_HIP_TRY(hipMemcpyAsync(&merged, d_cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
+        MGX_HIP_TRY(hipMemcpyAsync(rcomm_h.data(), d_rcomm, nv * 4, hipMemcpyDeviceToHost,
+                                   ctx->stream));
+        MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
+      }
 
       // global refined community id per node: the member slot of its local
       // refined community (== another node's global member position)
@@ -885,7 +887,7 @@ extern "C" mgx_status mgx_leiden(mgx_context *ctx, mgx_graph *g, double gamma,
         }
 
         // upload the new level
-        free_level(&L);
+        free_level(own, &L);
         L.nv = n_new;
         std::vector<uint32_t> rp_up(n_new + 1, 0);
         std::vector<int32_t> col_up;
@@ -898,10 +900,7 @@ extern "C" mgx_status mgx_leiden(mgx_context *ctx, mgx_graph *g, double gamma,
           rp_up[i2 + 1] = (uint32_t)col_up.size();
         }
         L.ne2 = (int64_t)col_up.size();
-        MGX_HIP_TRY(mgx_hip_malloc(&L.row_ptr, (n_new + 1) * 4));
-        MGX_HIP_TRY(mgx_hip_malloc(&L.col, (L.ne2 ? L.ne2 : 1) * 4));
-        MGX_HIP_TRY(mgx_hip_malloc(&L.w, (L.ne2 ? L.ne2 : 1) * 8));
-        MGX_HIP_TRY(mgx_hip_malloc(&L.node_w, n_new * 8));
+        MGX_TRY(alloc_level(own, &L));
         MGX_HIP_TRY(hipMemcpyAsync(L.row_ptr, rp_up.data(), (n_new + 1) * 4,
                                    hipMemcpyHostToDevice, ctx->stream));
         if (L.ne2) {
@@ -912,10 +911,10 @@ extern "C" mgx_status mgx_leiden(mgx_context *ctx, mgx_graph *g, double gamma,
         }
         MGX_HIP_TRY(hipMemcpyAsync(L.node_w, nw_new.data(), n_new * 8,
                                    hipMemcpyHostToDevice, ctx->stream));
-        (void)hipFree(d_comm);
-        (void)hipFree(d_csize);
-        MGX_HIP_TRY(mgx_hip_malloc(&d_comm, n_new * 4));
-        MGX_HIP_TRY(mgx_hip_malloc(&d_csize, n_new * 4));
+        own.release(d_comm);
+        own.release(d_csize);
+        MGX_TRY(own.alloc_plain(&d_comm, n_new));
+        MGX_TRY(own.alloc_plain(&d_csize, n_new));
         MGX_HIP_TRY(hipMemcpyAsync(d_comm, comm_new.data(), n_new * 4,
                                    hipMemcpyHostToDevice, ctx->stream));
         std::vector<uint32_t> cs_new((size_t)n_new, 0);
@@ -929,18 +928,8 @@ extern "C" mgx_status mgx_leiden(mgx_context *ctx, mgx_graph *g, double gamma,
         ++level;
       }
     }
-    (void)hipFree(d_srows);
-    (void)hipFree(d_brows);
-    (void)hipFree(d_target);
-    (void)hipFree(d_poff);
-    (void)hipFree(d_pkeys);
-    (void)hipFree(d_pvals);
-    (void)hipFree(d_cnt);
     if (iters >= max_iterations) done = true;
   }
-  (void)hipFree(d_comm);
-  (void)hipFree(d_csize);
-  free_level(&L);
   if (st != MGX_OK) return st;
 
   // compose per-node hierarchies from the dendrogram levels

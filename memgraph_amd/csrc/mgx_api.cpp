@@ -1,6 +1,7 @@
 // libmgx_analytics host API: context/graph lifecycle, error reporting.
 // Compiled by hipcc as HIP host code (no kernels here).
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -139,6 +140,57 @@ void mgx_context::cache_trim() {
   cache_free_bytes = 0;
 }
 
+namespace {
+std::atomic<int64_t> g_scope_outstanding{0};
+std::atomic<int64_t> g_scope_fail_in{-1};  // allocations until the forced failure
+}  // namespace
+
+extern "C" int64_t mgx_test_scope_hook(int64_t fail_at) {
+  g_scope_fail_in.store(fail_at > 0 ? fail_at : -1);
+  return g_scope_outstanding.load();
+}
+
+mgx_status mgx_scope::take(void **p, size_t bytes, bool cached) {
+  if (g_scope_fail_in.load() > 0 && g_scope_fail_in.fetch_sub(1) == 1) {
+    g_scope_fail_in.store(-1);
+    mgx_set_error("scope allocation of %zu bytes failed by the test hook", bytes);
+    return MGX_ERR_OUT_OF_MEMORY;
+  }
+  if (cached) {
+    MGX_TRY(ctx->alloc_async(p, bytes));
+  } else if (hipError_t e = mgx_hip_malloc(p, bytes); e != hipSuccess) {
+    (void)hipGetLastError();
+    mgx_set_error("mgx_hip_malloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? MGX_ERR_OUT_OF_MEMORY : MGX_ERR_HIP;
+  }
+  owned.push_back({*p, cached});
+  ++g_scope_outstanding;
+  return MGX_OK;
+}
+
+static void scope_free(mgx_context *ctx, void *p, bool cached) {
+  if (cached) {
+    (void)ctx->free_async(p);
+  } else {
+    (void)hipFree(p);
+  }
+}
+
+void mgx_scope::drop(void *p, bool free_it) {
+  for (size_t i = owned.size(); i-- > 0;) {
+    if (owned[i].first != p) continue;
+    if (free_it) scope_free(ctx, p, owned[i].second);
+    owned.erase(owned.begin() + i);
+    --g_scope_outstanding;
+    return;
+  }
+}
+
+mgx_scope::~mgx_scope() {  // in allocation order, as the hand-written lists freed
+  for (auto &b : owned) scope_free(ctx, b.first, b.second);
+  g_scope_outstanding -= (int64_t)owned.size();
+}
+
 mgx_status mgx_context::reserve(size_t bytes, void **out) {
   if (bytes > workspace_bytes) {
     // Drain queued users of the old workspace before recycling it; growth
@@ -189,7 +241,7 @@ extern "C" mgx_status mgx_destroy(mgx_context *ctx) {
   }
   if (ctx->workspace) (void)ctx->free_async(ctx->workspace);
   ctx->cache_trim();
-  for (auto &e : ctx->cache_live) (void)hipFree(e.first);  // leaked by callers
+  for (auto &e : ctx->cache_live) (void)hipFree(e.first);  // still held, e.g. by an unfinished run
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
   return MGX_OK;
@@ -202,7 +254,7 @@ extern "C" mgx_status mgx_sync(mgx_context *ctx) {
 }
 
 // graph_build.hip
-mgx_status mgx_upload_coo(mgx_context *ctx, const int64_t *src, const int64_t *dst,
+mgx_status mgx_upload_coo(mgx_scope &own, const int64_t *src, const int64_t *dst,
                           const double *weights, int64_t n_edges, int32_t **d_src,
                           int32_t **d_dst, float **d_w);
 
@@ -238,17 +290,20 @@ extern "C" mgx_status mgx_graph_from_coo(mgx_context *ctx, const int64_t *src,
       return MGX_ERR_INVALID_ARGUMENT;
     }
   }
-  int32_t *d_src = nullptr, *d_dst = nullptr;
-  float *d_w = nullptr;
-  MGX_TRY(mgx_upload_coo(ctx, src, dst, weights, n_edges, &d_src, &d_dst, &d_w));
-  auto *g = new mgx_graph();
-  mgx_status s = mgx_build_from_device_coo(ctx, d_src, d_dst, d_w, n_vertices, n_edges,
-                                           flags, g);
-  (void)hipFree(d_src);
-  (void)hipFree(d_dst);
-  if (d_w) (void)hipFree(d_w);
+  mgx_graph *g = nullptr;
+  mgx_status s;
+  {
+    mgx_scope coo(ctx);
+    int32_t *d_src = nullptr, *d_dst = nullptr;
+    float *d_w = nullptr;
+    s = mgx_upload_coo(coo, src, dst, weights, n_edges, &d_src, &d_dst, &d_w);
+    if (s == MGX_OK) {
+      g = new mgx_graph();
+      s = mgx_build_from_device_coo(ctx, d_src, d_dst, d_w, n_vertices, n_edges, flags, g);
+    }
+  }
   if (s != MGX_OK) {
-    (void)mgx_graph_destroy(ctx, g);
+    if (g) (void)mgx_graph_destroy(ctx, g);
     return s;
   }
   *out = g;
@@ -262,28 +317,28 @@ mgx_status build_generated(mgx_context *ctx, int64_t n_vertices, int64_t n_edges
                            uint64_t seed, double a, double b, double c, mgx_graph **out) {
   MGX_TRY(check_sizes(n_vertices, n_edges));
   MGX_HIP_TRY(hipSetDevice(ctx->device));
-  int32_t *d_src = nullptr, *d_dst = nullptr;
-  float *d_w = nullptr;
-  MGX_TRY(ctx->alloc_async((void **)&d_src, n_edges * sizeof(int32_t)));
-  MGX_TRY(ctx->alloc_async((void **)&d_dst, n_edges * sizeof(int32_t)));
-  mgx_status s;
-  if (rmat) {
-    s = mgx_gen_rmat_device(ctx, scale, n_edges, seed, a, b, c, d_src, d_dst);
-  } else {
-    s = mgx_gen_uniform_device(ctx, n_vertices, n_edges, seed, d_src, d_dst);
-  }
-  if (s == MGX_OK && (flags & MGX_BUILD_WEIGHTED)) {
-    MGX_TRY(ctx->alloc_async((void **)&d_w, n_edges * sizeof(float)));
-    s = mgx_gen_weights_device(ctx, n_edges, weight_seed, d_w);
-  }
   mgx_graph *g = nullptr;
-  if (s == MGX_OK) {
-    g = new mgx_graph();
-    s = mgx_build_from_device_coo(ctx, d_src, d_dst, d_w, n_vertices, n_edges, flags, g);
+  mgx_status s;
+  {
+    mgx_scope coo(ctx);
+    int32_t *d_src = nullptr, *d_dst = nullptr;
+    float *d_w = nullptr;
+    MGX_TRY(coo.alloc(&d_src, n_edges));
+    MGX_TRY(coo.alloc(&d_dst, n_edges));
+    if (rmat) {
+      s = mgx_gen_rmat_device(ctx, scale, n_edges, seed, a, b, c, d_src, d_dst);
+    } else {
+      s = mgx_gen_uniform_device(ctx, n_vertices, n_edges, seed, d_src, d_dst);
+    }
+    if (s == MGX_OK && (flags & MGX_BUILD_WEIGHTED)) {
+      MGX_TRY(coo.alloc(&d_w, n_edges));
+      s = mgx_gen_weights_device(ctx, n_edges, weight_seed, d_w);
+    }
+    if (s == MGX_OK) {
+      g = new mgx_graph();
+      s = mgx_build_from_device_coo(ctx, d_src, d_dst, d_w, n_vertices, n_edges, flags, g);
+    }
   }
-  (void)ctx->free_async(d_src);
-  (void)ctx->free_async(d_dst);
-  if (d_w) (void)ctx->free_async(d_w);
   if (s != MGX_OK) {
     if (g) (void)mgx_graph_destroy(ctx, g);
     return s;
@@ -323,21 +378,23 @@ extern "C" mgx_status mgx_graph_rmat_sharded(mgx_context *ctx, int scale, int64_
     return MGX_ERR_INVALID_ARGUMENT;
   }
   MGX_HIP_TRY(hipSetDevice(ctx->device));
-  int32_t *d_src = nullptr, *d_dst = nullptr;
-  MGX_HIP_TRY(mgx_hip_malloc(&d_src, (n_edges > 0 ? n_edges : 1) * sizeof(int32_t)));
-  MGX_HIP_TRY(mgx_hip_malloc(&d_dst, (n_edges > 0 ? n_edges : 1) * sizeof(int32_t)));
-  mgx_status s = mgx_gen_rmat_device(ctx, scale, n_edges, seed, a, b, c, d_src, d_dst);
   mgx_graph *g = nullptr;
-  if (s == MGX_OK) {
-    g = new mgx_graph();
-    const int64_t clamped_end = row_end < V ? row_end : V;
-    s = mgx_build_sharded_in_csr(ctx, d_src, d_dst, V, n_edges, row_begin, clamped_end, g);
+  mgx_status s;
+  {
+    mgx_scope coo(ctx);
+    int32_t *d_src = nullptr, *d_dst = nullptr;
+    MGX_TRY(coo.alloc_plain(&d_src, n_edges));
+    MGX_TRY(coo.alloc_plain(&d_dst, n_edges));
+    s = mgx_gen_rmat_device(ctx, scale, n_edges, seed, a, b, c, d_src, d_dst);
     if (s == MGX_OK) {
-      g->row_end = row_end;  // keep the padded shard size for allgather
+      g = new mgx_graph();
+      const int64_t clamped_end = row_end < V ? row_end : V;
+      s = mgx_build_sharded_in_csr(ctx, d_src, d_dst, V, n_edges, row_begin, clamped_end, g);
+      if (s == MGX_OK) {
+        g->row_end = row_end;  // keep the padded shard size for allgather
+      }
     }
   }
-  (void)hipFree(d_src);
-  (void)hipFree(d_dst);
   if (s != MGX_OK) {
     if (g) (void)mgx_graph_destroy(ctx, g);
     return s;

@@ -101,6 +101,42 @@ struct mgx_context {
   mgx_status reserve(size_t bytes, void **out);
 };
 
+// Owner of the transient device buffers of a function or block: what it still
+// holds when it goes out of scope is released, on every return path (a release
+// that fails there is ignored). A count of 0 allocates one element.
+struct mgx_scope {
+  mgx_context *ctx;
+  std::vector<std::pair<void *, bool>> owned;  // block, whether from the cache
+  explicit mgx_scope(mgx_context *c) : ctx(c) {}
+  mgx_scope(const mgx_scope &) = delete;
+  mgx_scope &operator=(const mgx_scope &) = delete;
+  ~mgx_scope();
+  template <typename T>
+  mgx_status alloc(T **p, int64_t count) {  // ctx->alloc_async / free_async
+    return take((void **)p, (size_t)(count > 0 ? count : 1) * sizeof(T), true);
+  }
+  template <typename T>
+  mgx_status alloc_plain(T **p, int64_t count) {  // mgx_hip_malloc / hipFree
+    return take((void **)p, (size_t)(count > 0 ? count : 1) * sizeof(T), false);
+  }
+  void release(void *p) { drop(p, true); }  // free p now
+  // Stop owning p without freeing it; returns p, for the line that stores it
+  // into whatever owns it from then on.
+  template <typename T>
+  T *give_up(T *p) {
+    drop(p, false);
+    return p;
+  }
+  mgx_status take(void **p, size_t bytes, bool cached);
+  void drop(void *p, bool free_it);
+};
+
+// Test support, not part of the public ABI. Returns how many blocks all the
+// scopes of the process own right now, then arms the failure countdown: the
+// fail_at-th scope allocation from now on returns MGX_ERR_OUT_OF_MEMORY on
+// the host, before any HIP call; -1 disarms it.
+extern "C" int64_t mgx_test_scope_hook(int64_t fail_at);
+
 // Degree bins for the fused sweep kernels. Rows are classified by degree;
 // within a bin rows are in ascending id order (stable 2-bit radix sort) so
 // adjacent lanes read adjacent CSR ranges.
@@ -231,6 +267,10 @@ mgx_status mgx_build_bins(mgx_context *ctx, const uint32_t *row_ptr, int64_t row
 // zero degree are dropped unless include_zero, and then lead bin0 (n_zero).
 mgx_status mgx_build_bins_range(mgx_context *ctx, const uint32_t *lo, const uint32_t *hi,
                                 int64_t rows, bool include_zero, mgx_bins *bins);
+// The same for a work list that is itself transient: bins->rows belongs to the
+// caller's scope `own`.
+mgx_status mgx_build_bins_range(mgx_scope &own, const uint32_t *lo, const uint32_t *hi,
+                                int64_t rows, bool include_zero, mgx_bins *bins);
 // Source-stripe the (sorted) in-CSR of g; n_stripes chosen from V (env
 // MGX_PR_STRIPES overrides; 1 = disabled). When g->xcd is set (decided
 // before the renumbering, see mgx_xcd_wanted) it builds the heavy-row XCD
@@ -292,9 +332,9 @@ mgx_status mgx_pagerank_normalize_download(mgx_pagerank_run *run, double *out_ra
 mgx_status mgx_wcc_impl(mgx_context *ctx, mgx_graph *g, int64_t *out_component,
                         int64_t *n_components);
 // Device-output form (bridges.hip): min-member labels, label[v] = smallest id
-// of v's component, in a context allocation of V int32 that the caller frees.
-// Needs V > 0 and the sym-CSR; has synchronized when it returns.
-mgx_status mgx_wcc_labels_device(mgx_context *ctx, mgx_graph *g, int32_t **out_label);
+// of v's component, in a context allocation of V int32 that the caller's scope
+// `own` owns. Needs V > 0 and the sym-CSR; has synchronized when it returns.
+mgx_status mgx_wcc_labels_device(mgx_scope &own, mgx_graph *g, int32_t **out_label);
 // katz.hip
 mgx_status mgx_katz_impl(mgx_context *ctx, mgx_graph *g, double alpha, double epsilon,
                          double *out_centrality, int64_t *iterations);

@@ -243,9 +243,10 @@ mgx_status ensure_pool(mgx_context *ctx, int64_t need_cap) {
   while (cap < need_cap) cap *= 2;
   uint32_t *nw = nullptr, *np = nullptr;
   int32_t *nn = nullptr;
-  MGX_HIP_TRY(mgx_hip_malloc(&nw, cap * 4));
-  MGX_HIP_TRY(mgx_hip_malloc(&np, cap * 4));
-  MGX_HIP_TRY(mgx_hip_malloc(&nn, cap * 4));
+  mgx_scope grown(ctx);
+  MGX_TRY(grown.alloc_plain(&nw, cap));
+  MGX_TRY(grown.alloc_plain(&np, cap));
+  MGX_TRY(grown.alloc_plain(&nn, cap));
   if (g_st.pool_used > 0) {
     MGX_HIP_TRY(hipMemcpyAsync(nw, g_st.e_walk, g_st.pool_used * 4,
                                hipMemcpyDeviceToDevice, ctx->stream));
@@ -258,9 +259,9 @@ mgx_status ensure_pool(mgx_context *ctx, int64_t need_cap) {
   if (g_st.e_walk) (void)hipFree(g_st.e_walk);
   if (g_st.e_pos) (void)hipFree(g_st.e_pos);
   if (g_st.e_node) (void)hipFree(g_st.e_node);
-  g_st.e_walk = nw;
-  g_st.e_pos = np;
-  g_st.e_node = nn;
+  g_st.e_walk = grown.give_up(nw);
+  g_st.e_pos = grown.give_up(np);
+  g_st.e_node = grown.give_up(nn);
   g_st.pool_cap = cap;
   return MGX_OK;
 }
@@ -272,9 +273,10 @@ mgx_status ensure_walks(mgx_context *ctx, int64_t need) {
   int32_t *ns = nullptr;
   uint32_t *ng = nullptr;
   uint8_t *nd = nullptr;
-  MGX_HIP_TRY(mgx_hip_malloc(&ns, cap * 4));
-  MGX_HIP_TRY(mgx_hip_malloc(&ng, cap * 4));
-  MGX_HIP_TRY(mgx_hip_malloc(&nd, cap));
+  mgx_scope grown(ctx);
+  MGX_TRY(grown.alloc_plain(&ns, cap));
+  MGX_TRY(grown.alloc_plain(&ng, cap));
+  MGX_TRY(grown.alloc_plain(&nd, cap));
   MGX_HIP_TRY(hipMemsetAsync(ng, 0, cap * 4, ctx->stream));
   MGX_HIP_TRY(hipMemsetAsync(nd, 0, cap, ctx->stream));
   if (g_st.n_walks > 0) {
@@ -289,9 +291,9 @@ mgx_status ensure_walks(mgx_context *ctx, int64_t need) {
   if (g_st.w_start) (void)hipFree(g_st.w_start);
   if (g_st.w_gen) (void)hipFree(g_st.w_gen);
   if (g_st.w_dead) (void)hipFree(g_st.w_dead);
-  g_st.w_start = ns;
-  g_st.w_gen = ng;
-  g_st.w_dead = nd;
+  g_st.w_start = grown.give_up(ns);
+  g_st.w_gen = grown.give_up(ng);
+  g_st.w_dead = grown.give_up(nd);
   g_st.walks_cap = cap;
   return MGX_OK;
 }
@@ -441,8 +443,9 @@ mgx_status compute_rank(mgx_context *ctx, const Maps &m, double *out_rank) {
   MGX_TRY(sync_slot_alive(ctx));
   uint32_t *counter = nullptr;
   unsigned long long *d_sum = nullptr;
-  MGX_TRY(ctx->alloc_async((void **)&counter, (n_slots > 0 ? n_slots : 1) * 4));
-  MGX_TRY(ctx->alloc_async((void **)&d_sum, 8));
+  mgx_scope bufs(ctx);
+  MGX_TRY(bufs.alloc(&counter, n_slots));
+  MGX_TRY(bufs.alloc(&d_sum, 1));
   MGX_HIP_TRY(hipMemsetAsync(counter, 0, (n_slots > 0 ? n_slots : 1) * 4, ctx->stream));
   MGX_HIP_TRY(hipMemsetAsync(d_sum, 0, 8, ctx->stream));
   if (g_st.pool_used > 0)
@@ -453,18 +456,16 @@ mgx_status compute_rank(mgx_context *ctx, const Maps &m, double *out_rank) {
     hipLaunchKernelGGL(k_sum_u32, dim3((uint32_t)grid_for(n_slots)), dim3(kBlock), 0,
                        ctx->stream, n_slots, counter, d_sum);
   if (out_rank && m.V > 0) {
+    mgx_scope rank_bufs(ctx);
     double *d_rank = nullptr;
-    MGX_TRY(ctx->alloc_async((void **)&d_rank, m.V * 8));
+    MGX_TRY(rank_bufs.alloc(&d_rank, m.V));
     hipLaunchKernelGGL(k_rank_out, dim3((uint32_t)grid_for(m.V)), dim3(kBlock), 0,
                        ctx->stream, m.V, m.dense2slot, counter, d_sum, d_rank);
     MGX_HIP_TRY(hipMemcpyAsync(out_rank, d_rank, m.V * 8, hipMemcpyDeviceToHost,
                                ctx->stream));
     MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    MGX_TRY(ctx->free_async(d_rank));
   }
   MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  MGX_TRY(ctx->free_async(counter));
-  MGX_TRY(ctx->free_async(d_sum));
   return MGX_OK;
 }
 
@@ -490,16 +491,15 @@ mgx_status spawn_walks(mgx_context *ctx, const Maps &m, mgx_graph *g,
   }
   MGX_HIP_TRY(hipMemcpyAsync(g_st.w_start + g_st.n_walks, wstart.data(), n_new * 4,
                              hipMemcpyHostToDevice, ctx->stream));
+  mgx_scope bufs(ctx);
   GenItem *d_items = nullptr;
-  MGX_TRY(ctx->alloc_async((void **)&d_items, n_new * sizeof(GenItem)));
+  MGX_TRY(bufs.alloc(&d_items, n_new));
   MGX_HIP_TRY(hipMemcpyAsync(d_items, items.data(), n_new * sizeof(GenItem),
                              hipMemcpyHostToDevice, ctx->stream));
   MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
   g_st.n_walks += n_new;
   const int64_t expect = n_new * (int64_t)(2.0 / (g_st.eps > 0.01 ? g_st.eps : 0.01) + 2);
-  mgx_status s = run_gen(ctx, m, g, d_items, n_new, g_st.eps, expect);
-  (void)ctx->free_async(d_items);
-  return s;
+  return run_gen(ctx, m, g, d_items, n_new, g_st.eps, expect);
 }
 
 // Truncate-and-regrow for one changed edge's `from` endpoint
@@ -510,9 +510,10 @@ mgx_status rewire_from(mgx_context *ctx, const Maps &m, mgx_graph *g, int32_t fr
   uint32_t *minpos = nullptr;
   uint32_t *aff = nullptr;
   unsigned long long *n_aff_d = nullptr;
-  MGX_TRY(ctx->alloc_async((void **)&minpos, g_st.n_walks * 4));
-  MGX_TRY(ctx->alloc_async((void **)&aff, g_st.n_walks * 4));
-  MGX_TRY(ctx->alloc_async((void **)&n_aff_d, 8));
+  mgx_scope bufs(ctx);
+  MGX_TRY(bufs.alloc(&minpos, g_st.n_walks));
+  MGX_TRY(bufs.alloc(&aff, g_st.n_walks));
+  MGX_TRY(bufs.alloc(&n_aff_d, 1));
   MGX_HIP_TRY(hipMemsetAsync(minpos, 0xFF, g_st.n_walks * 4, ctx->stream));
   MGX_HIP_TRY(hipMemsetAsync(n_aff_d, 0, 8, ctx->stream));
   hipLaunchKernelGGL(k_find_affected, dim3((uint32_t)grid_for(g_st.pool_used)),
@@ -528,19 +529,16 @@ mgx_status rewire_from(mgx_context *ctx, const Maps &m, mgx_graph *g, int32_t fr
   MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
   mgx_status s = MGX_OK;
   if (n_aff > 0 && from_exists) {
+    mgx_scope item_bufs(ctx);
     GenItem *d_items = nullptr;
-    MGX_TRY(ctx->alloc_async((void **)&d_items, n_aff * sizeof(GenItem)));
+    MGX_TRY(item_bufs.alloc(&d_items, (int64_t)n_aff));
     hipLaunchKernelGGL(k_make_regrow_items, dim3((uint32_t)grid_for((int64_t)n_aff)),
                        dim3(kBlock), 0, ctx->stream, (int64_t)n_aff, aff, minpos,
                        from_slot, g_st.w_gen, d_items);
     const int64_t expect =
         (int64_t)n_aff * (int64_t)(4.0 / (g_st.eps > 0.01 ? g_st.eps : 0.01) + 2);
     s = run_gen(ctx, m, g, d_items, (int64_t)n_aff, g_st.eps / 2.0, expect);
-    (void)ctx->free_async(d_items);
   }
-  (void)ctx->free_async(minpos);
-  (void)ctx->free_async(aff);
-  (void)ctx->free_async(n_aff_d);
   return s;
 }
 
@@ -672,8 +670,9 @@ extern "C" mgx_status mgx_pronline_stats(mgx_context *ctx, int64_t *n_walks,
   if (n_live_entries) {
     *n_live_entries = 0;
     if (g_st.pool_used > 0) {
+      mgx_scope bufs(ctx);
       unsigned long long *d = nullptr;
-      MGX_TRY(ctx->alloc_async((void **)&d, 8));
+      MGX_TRY(bufs.alloc(&d, 1));
       MGX_HIP_TRY(hipMemsetAsync(d, 0, 8, ctx->stream));
       hipLaunchKernelGGL(k_count_live, dim3((uint32_t)grid_for(g_st.pool_used)),
                          dim3(kBlock), 0, ctx->stream, g_st.pool_used, g_st.e_node,
@@ -681,7 +680,6 @@ extern "C" mgx_status mgx_pronline_stats(mgx_context *ctx, int64_t *n_walks,
       unsigned long long out = 0;
       MGX_HIP_TRY(hipMemcpyAsync(&out, d, 8, hipMemcpyDeviceToHost, ctx->stream));
       MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-      (void)ctx->free_async(d);
       *n_live_entries = (int64_t)out;
     }
   }

@@ -103,9 +103,10 @@ mgx_status build_distinct_view(mgx_context *ctx, mgx_graph *g) {
     g->uniq_alias = true;
     return MGX_OK;
   }
+  mgx_scope bufs(ctx);
   uint32_t *flag = nullptr, *pos = nullptr;
-  MGX_TRY(ctx->alloc_async((void **)&flag, E * sizeof(uint32_t)));
-  MGX_TRY(ctx->alloc_async((void **)&pos, E * sizeof(uint32_t)));
+  MGX_TRY(bufs.alloc(&flag, E));
+  MGX_TRY(bufs.alloc(&pos, E));
   hipLaunchKernelGGL(k_flag_new, dim3((uint32_t)grid_for(E, kGridCap)), dim3(kBlock), 0,
                      ctx->stream, E, g->out_col, flag);
   hipLaunchKernelGGL(k_flag_row_start, dim3((uint32_t)grid_for(V, kGridCap)), dim3(kBlock), 0,
@@ -126,24 +127,17 @@ mgx_status build_distinct_view(mgx_context *ctx, mgx_graph *g) {
   } else {
     uint32_t *rp = nullptr;
     int32_t *uc = nullptr;
-    MGX_HIP_TRY(mgx_hip_malloc(&rp, (V + 1) * sizeof(uint32_t)));
-    if (mgx_hip_malloc(&uc, total * sizeof(int32_t)) != hipSuccess) {
-      (void)hipGetLastError();
-      (void)hipFree(rp);
-      mgx_set_error("similarity: distinct view allocation failed");
-      return MGX_ERR_OUT_OF_MEMORY;
-    }
+    MGX_TRY(bufs.alloc_plain(&rp, V + 1));
+    MGX_TRY(bufs.alloc_plain(&uc, total));
     hipLaunchKernelGGL(k_compact, dim3((uint32_t)grid_for(E, kGridCap)), dim3(kBlock), 0,
                        ctx->stream, E, g->out_col, flag, pos, uc);
     hipLaunchKernelGGL(k_uniq_row_ptr, dim3((uint32_t)grid_for(V + 1, kGridCap)), dim3(kBlock),
                        0, ctx->stream, V, E, (uint32_t)total, g->out_row_ptr, pos, rp);
-    g->uniq_row_ptr = rp;
-    g->uniq_col = uc;
+    g->uniq_row_ptr = bufs.give_up(rp);
+    g->uniq_col = bufs.give_up(uc);
     g->uniq_alias = false;
   }
   g->uniq_entries = total;
-  MGX_TRY(ctx->free_async(flag));
-  MGX_TRY(ctx->free_async(pos));
   MGX_HIP_TRY(hipGetLastError());
   return MGX_OK;
 }
@@ -499,17 +493,18 @@ mgx_status mgx_similarity_pairs_impl(mgx_context *ctx, mgx_graph *g, int metric,
   uint32_t *lo_s = nullptr, *hi_s = nullptr, *lo_m = nullptr, *hi_m = nullptr;
   int64_t *d_common = nullptr;
   double *d_sim = nullptr;
-  MGX_TRY(ctx->alloc_async((void **)&d_uv, 2 * n * sizeof(int32_t)));
+  mgx_scope bufs(ctx);
+  MGX_TRY(bufs.alloc(&d_uv, 2 * n));
   if (want_s) {
-    MGX_TRY(ctx->alloc_async((void **)&lo_s, n * sizeof(uint32_t)));
-    MGX_TRY(ctx->alloc_async((void **)&hi_s, n * sizeof(uint32_t)));
+    MGX_TRY(bufs.alloc(&lo_s, n));
+    MGX_TRY(bufs.alloc(&hi_s, n));
   }
   if (want_m) {
-    MGX_TRY(ctx->alloc_async((void **)&lo_m, n * sizeof(uint32_t)));
-    MGX_TRY(ctx->alloc_async((void **)&hi_m, n * sizeof(uint32_t)));
+    MGX_TRY(bufs.alloc(&lo_m, n));
+    MGX_TRY(bufs.alloc(&hi_m, n));
   }
-  MGX_TRY(ctx->alloc_async((void **)&d_common, n * sizeof(int64_t)));
-  MGX_TRY(ctx->alloc_async((void **)&d_sim, n * sizeof(double)));
+  MGX_TRY(bufs.alloc(&d_common, n));
+  MGX_TRY(bufs.alloc(&d_sim, n));
   MGX_HIP_TRY(hipMemcpyAsync(d_uv, h_uv.data(), 2 * n * sizeof(int32_t), hipMemcpyHostToDevice,
                              ctx->stream));
   // Pairs with an empty shorter row are dropped by the binning: their
@@ -520,18 +515,10 @@ mgx_status mgx_similarity_pairs_impl(mgx_context *ctx, mgx_graph *g, int metric,
                      ctx->stream, n, g->uniq_row_ptr, d_uv, d_uv + n, mode, lo_s, hi_s, lo_m,
                      hi_m);
   mgx_bins bins_s, bins_m;
-  mgx_status st = MGX_OK;
-  if (want_s) st = mgx_build_bins_range(ctx, lo_s, hi_s, n, /*include_zero=*/false, &bins_s);
-  if (st == MGX_OK && want_m)
-    st = mgx_build_bins_range(ctx, lo_m, hi_m, n, /*include_zero=*/false, &bins_m);
-  auto free_bins = [&]() {
-    if (bins_s.rows) (void)hipFree(bins_s.rows);
-    if (bins_m.rows) (void)hipFree(bins_m.rows);
-  };
-  if (st != MGX_OK) {
-    free_bins();
-    return st;
-  }
+  if (want_s)
+    MGX_TRY(mgx_build_bins_range(bufs, lo_s, hi_s, n, /*include_zero=*/false, &bins_s));
+  if (want_m)
+    MGX_TRY(mgx_build_bins_range(bufs, lo_m, hi_m, n, /*include_zero=*/false, &bins_m));
   MGX_HIP_TRY(hipEventRecord(prep.b, ctx->stream));
 
   PairArgs A;
@@ -560,9 +547,7 @@ mgx_status mgx_similarity_pairs_impl(mgx_context *ctx, mgx_graph *g, int metric,
   if (out_common)
     MGX_HIP_TRY(hipMemcpyAsync(out_common, d_common, n * sizeof(int64_t),
                                hipMemcpyDeviceToHost, ctx->stream));
-  hipError_t sync_err = hipStreamSynchronize(ctx->stream);
-  free_bins();
-  MGX_HIP_TRY(sync_err);
+  MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
   if (stats) {
     stats->pairs = n;
     for (int b = 0; b < 4; ++b) {
@@ -573,13 +558,6 @@ mgx_status mgx_similarity_pairs_impl(mgx_context *ctx, mgx_graph *g, int metric,
     MGX_TRY(prep.ms(&stats->prep_ms));
     MGX_TRY(run.ms(&stats->ms));
   }
-  MGX_TRY(ctx->free_async(d_uv));
-  MGX_TRY(ctx->free_async(lo_s));
-  MGX_TRY(ctx->free_async(hi_s));
-  MGX_TRY(ctx->free_async(lo_m));
-  MGX_TRY(ctx->free_async(hi_m));
-  MGX_TRY(ctx->free_async(d_common));
-  MGX_TRY(ctx->free_async(d_sim));
   MGX_HIP_TRY(hipGetLastError());
   return MGX_OK;
 }
@@ -610,7 +588,8 @@ mgx_status mgx_similarity_all_impl(mgx_context *ctx, mgx_graph *g, int metric, d
   const int64_t cap = std::max(env_positive("MGX_SIM_CHUNK_PAIRS", kDefaultChunkPairs), V - 1);
   const int64_t staging_pairs = std::min(cap, total);
   double *d_out = nullptr;
-  MGX_TRY(ctx->alloc_async((void **)&d_out, staging_pairs * sizeof(double)));
+  mgx_scope bufs(ctx);
+  MGX_TRY(bufs.alloc(&d_out, staging_pairs));
   MGX_HIP_TRY(hipEventRecord(prep.b, ctx->stream));
 
   AllArgs A;
@@ -657,7 +636,6 @@ mgx_status mgx_similarity_all_impl(mgx_context *ctx, mgx_graph *g, int metric, d
     stats->ms = ms_acc;
     MGX_TRY(prep.ms(&stats->prep_ms));
   }
-  MGX_TRY(ctx->free_async(d_out));
   MGX_HIP_TRY(hipGetLastError());
   return MGX_OK;
 }

@@ -84,14 +84,17 @@ __global__ void k_wcc_emit(int64_t n, const int32_t *label, const uint32_t *scan
 }  // namespace
 
 // Min-member labels left on the device: *out_label is a context allocation
-// of V int32 that the caller frees (V > 0, sym-CSR present; all work is queued
-// on ctx->stream and the fixpoint loop has synchronized when this returns).
-mgx_status mgx_wcc_labels_device(mgx_context *ctx, mgx_graph *g, int32_t **out_label) {
+// of V int32 owned by the caller's scope `own` (V > 0, sym-CSR present; all
+// work is queued on ctx->stream and the fixpoint loop has synchronized when
+// this returns).
+mgx_status mgx_wcc_labels_device(mgx_scope &own, mgx_graph *g, int32_t **out_label) {
+  mgx_context *ctx = own.ctx;
   const int64_t V = g->n_vertices;
+  mgx_scope bufs(ctx);
   int32_t *label = nullptr;
   uint32_t *d_changed = nullptr;
-  MGX_TRY(ctx->alloc_async((void **)&label, V * sizeof(int32_t)));
-  MGX_TRY(ctx->alloc_async((void **)&d_changed, sizeof(uint32_t)));
+  MGX_TRY(own.alloc(&label, V));
+  MGX_TRY(bufs.alloc(&d_changed, 1));
   hipLaunchKernelGGL(mgx_k_iota<int32_t>, dim3((uint32_t)grid_for(V)), dim3(kBlock), 0,
                      ctx->stream, V, label);
 
@@ -113,7 +116,6 @@ mgx_status mgx_wcc_labels_device(mgx_context *ctx, mgx_graph *g, int32_t **out_l
                                ctx->stream));
     MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
   }
-  MGX_TRY(ctx->free_async(d_changed));
   *out_label = label;
   return MGX_OK;
 }
@@ -130,13 +132,14 @@ mgx_status mgx_wcc_impl(mgx_context *ctx, mgx_graph *g, int64_t *out_component,
     return MGX_OK;
   }
 
+  mgx_scope bufs(ctx);
   int32_t *label = nullptr;
-  MGX_TRY(mgx_wcc_labels_device(ctx, g, &label));
+  MGX_TRY(mgx_wcc_labels_device(bufs, g, &label));
 
   // Renumber + count.
   uint32_t *flag = nullptr, *scan = nullptr;
-  MGX_TRY(ctx->alloc_async((void **)&flag, V * sizeof(uint32_t)));
-  MGX_TRY(ctx->alloc_async((void **)&scan, (V + 1) * sizeof(uint32_t)));
+  MGX_TRY(bufs.alloc(&flag, V));
+  MGX_TRY(bufs.alloc(&scan, V + 1));
   hipLaunchKernelGGL(k_wcc_flag_roots, dim3((uint32_t)grid_for(V)), dim3(kBlock), 0,
                      ctx->stream, V, label, flag);
   MGX_TRY(mgx_with_temp(ctx, "wcc root scan", [&](void *tmp, size_t &bytes) {
@@ -145,7 +148,7 @@ mgx_status mgx_wcc_impl(mgx_context *ctx, mgx_graph *g, int64_t *out_component,
   }));
 
   int64_t *d_out = nullptr;
-  MGX_TRY(ctx->alloc_async((void **)&d_out, V * sizeof(int64_t)));
+  MGX_TRY(bufs.alloc(&d_out, V));
   hipLaunchKernelGGL(k_wcc_emit, dim3((uint32_t)grid_for(V)), dim3(kBlock), 0, ctx->stream,
                      V, label, scan, d_out);
   if (out_component) {
@@ -162,10 +165,6 @@ mgx_status mgx_wcc_impl(mgx_context *ctx, mgx_graph *g, int64_t *out_component,
     *n_components = (int64_t)last_scan + last_flag;
   }
   MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  MGX_TRY(ctx->free_async(label));
-  MGX_TRY(ctx->free_async(flag));
-  MGX_TRY(ctx->free_async(scan));
-  MGX_TRY(ctx->free_async(d_out));
   MGX_HIP_TRY(hipGetLastError());
   return MGX_OK;
 }

@@ -82,8 +82,13 @@ class SimilarityStats(ctypes.Structure):
     ]
 
 
+ERR_OUT_OF_MEMORY = 5
+
+
 class MgxError(RuntimeError):
-    pass
+    def __init__(self, message, status=None):
+        super().__init__(message)
+        self.status = status
 
 
 class Native:
@@ -105,7 +110,7 @@ class Native:
         if status != 0:
             msg = self.lib.mgx_status_string(status).decode()
             detail = self.lib.mgx_last_error().decode()
-            raise MgxError(f"{what}: {msg} ({detail})")
+            raise MgxError(f"{what}: {msg} ({detail})", status)
 
     def device_count(self):
         return self.lib.mgx_device_count()
@@ -120,6 +125,13 @@ class Native:
 
     def sync(self, ctx):
         self._check(self.lib.mgx_sync(ctx), "mgx_sync")
+
+    def test_scope_hook(self, fail_at=-1):
+        """Test support: device blocks the library's scopes own right now, in
+        the whole process. Then arms the fail_at-th scope allocation from now
+        on to fail as out of memory on the host; -1 disarms."""
+        self.lib.mgx_test_scope_hook.restype = ctypes.c_int64
+        return self.lib.mgx_test_scope_hook(ctypes.c_int64(fail_at))
 
     # --- graphs ---
     def graph_from_coo(self, ctx, src, dst, n_vertices, weights=None, flags=BUILD_IN_CSR):
