@@ -36,8 +36,9 @@
 //
 // Device layout per level: simple undirected CSR (u32 row_ptr, i32 col,
 // f64 w), fp64 node weights, i32 community ids + u32 community sizes.
-// Sweeps reuse the louvain.hip shape: LDS open-addressing tables for rows
-// under 256 neighbours, a global pool region per hub row.
+// Sweeps share louvain.hip's shape and its table (mgx_comm_table.h): LDS
+// open-addressing tables for rows under 256 neighbours, a global pool region
+// per hub row.
 
 #include <cstring>
 #include <unordered_map>
@@ -47,6 +48,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "../../include/mgx_graphgen.h"
+#include "mgx_comm_table.h"
 #include "mgx_device.h"
 
 namespace {
@@ -125,10 +127,13 @@ __device__ inline void leiden_move_finish(const MoveArgs &A, int32_t v, int32_t 
 
 // wave per small row, LDS table of (community, weight)
 __global__ void __launch_bounds__(kBlock) k_move_small(MoveArgs A) {
-  __shared__ int32_t keys[kBlock / 64][kLdsCap];
-  __shared__ double vals[kBlock / 64][kLdsCap];
+  __shared__ int32_t s_keys[kBlock / 64][kLdsCap];
+  __shared__ double s_vals[kBlock / 64][kLdsCap];
+  constexpr uint32_t mask = kLdsCap - 1;
   const int wave = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
+  int32_t *keys = s_keys[wave];
+  double *vals = s_vals[wave];
   const int64_t waves_per_grid = (int64_t)gridDim.x * (kBlock / 64);
   for (int64_t wi = (int64_t)blockIdx.x * (kBlock / 64) + wave; wi < A.n_small;
        wi += waves_per_grid) {
@@ -137,41 +142,22 @@ __global__ void __launch_bounds__(kBlock) k_move_small(MoveArgs A) {
     const uint32_t s = A.row_ptr[v], e = A.row_ptr[v + 1];
     const int32_t cv = A.comm[v];
     for (int t = lane; t < kLdsCap; t += 64) {
-      keys[wave][t] = -1;
-      vals[wave][t] = 0.0;
+      keys[t] = -1;
+      vals[t] = 0.0;
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    for (uint32_t j = s + lane; j < e; j += 64) {
-      const int32_t c = A.comm[A.col[j]];
-      uint32_t h = ((uint32_t)c * 2654435761u) & (kLdsCap - 1);
-      while (true) {
-        int32_t prev = atomicCAS(&keys[wave][h], -1, c);
-        if (prev == -1 || prev == c) break;
-        h = (h + 1) & (kLdsCap - 1);
-      }
-      atomicAdd(&vals[wave][h], A.w[j]);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wave_lds_fence();
+    for (uint32_t j = s + lane; j < e; j += 64)
+      comm_add(keys, vals, mask, A.comm[A.col[j]], A.w[j]);
+    wave_lds_fence();
     // current delta: w(v->C_v) - (|C_v|-1)*gamma (:88-90)
-    double wcv = 0.0;
-    {
-      uint32_t h = ((uint32_t)cv * 2654435761u) & (kLdsCap - 1);
-      for (int probe = 0; probe < kLdsCap; ++probe) {
-        const int32_t k = keys[wave][h];
-        if (k == cv) {
-          wcv = vals[wave][h];
-          break;
-        }
-        if (k == -1) break;
-        h = (h + 1) & (kLdsCap - 1);
-      }
-    }
+    bool found;
+    const double wcv = comm_find<true>(keys, vals, mask, kLdsCap, cv, &found);
     double best_delta = wcv - ((double)A.csize[cv] - 1.0) * A.gamma;
     int32_t best = cv;
     for (int t = lane; t < kLdsCap; t += 64) {
-      const int32_t c = keys[wave][t];
+      const int32_t c = keys[t];
       if (c >= 0 && c != cv) {
-        const double delta = vals[wave][t] - (double)A.csize[c] * A.gamma;
+        const double delta = vals[t] - (double)A.csize[c] * A.gamma;
         if (delta > best_delta + A.resolution ||
             (delta == best_delta + A.resolution && false)) {
           best_delta = delta;
@@ -189,7 +175,7 @@ __global__ void __launch_bounds__(kBlock) k_move_small(MoveArgs A) {
       }
     }
     if (lane == 0) leiden_move_finish(A, v, best);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wave_lds_fence();
   }
 }
 
@@ -203,6 +189,7 @@ __global__ void __launch_bounds__(kBlock) k_move_big(MoveArgs A) {
     const int32_t cv = A.comm[v];
     const uint64_t t0 = A.pool_off[bi], t1 = A.pool_off[bi + 1];
     const uint32_t cap = (uint32_t)(t1 - t0);
+    const uint32_t mask = cap - 1;
     int32_t *keys = A.pool_keys + t0;
     double *vals = A.pool_vals + t0;
     for (uint32_t t = threadIdx.x; t < cap; t += kBlock) {
@@ -210,30 +197,11 @@ __global__ void __launch_bounds__(kBlock) k_move_big(MoveArgs A) {
       vals[t] = 0.0;
     }
     __syncthreads();
-    for (uint32_t j = s + threadIdx.x; j < e; j += kBlock) {
-      const int32_t c = A.comm[A.col[j]];
-      uint32_t h = ((uint32_t)c * 2654435761u) & (cap - 1);
-      while (true) {
-        int32_t prev = atomicCAS(&keys[h], -1, c);
-        if (prev == -1 || prev == c) break;
-        h = (h + 1) & (cap - 1);
-      }
-      atomicAdd(&vals[h], A.w[j]);
-    }
+    for (uint32_t j = s + threadIdx.x; j < e; j += kBlock)
+      comm_add(keys, vals, mask, A.comm[A.col[j]], A.w[j]);
     __syncthreads();
-    double wcv = 0.0;
-    {
-      uint32_t h = ((uint32_t)cv * 2654435761u) & (cap - 1);
-      for (uint32_t probe = 0; probe < cap; ++probe) {
-        const int32_t k = keys[h];
-        if (k == cv) {
-          wcv = vals[h];
-          break;
-        }
-        if (k == -1) break;
-        h = (h + 1) & (cap - 1);
-      }
-    }
+    bool found;
+    const double wcv = comm_find<true>(keys, vals, mask, cap, cv, &found);
     double best_delta = wcv - ((double)A.csize[cv] - 1.0) * A.gamma;
     int32_t best = cv;
     for (uint32_t t = threadIdx.x; t < cap; t += kBlock) {

@@ -35,6 +35,7 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include "mgx_comm_table.h"
 #include "mgx_device.h"
 
 namespace {
@@ -42,73 +43,23 @@ namespace {
 constexpr uint32_t kSmallRowDeg = 256;  // <: wave+LDS table; >=: block+pool
 constexpr int kLdsCap = 512;            // per-wave table entries (>= 2*255)
 
-inline bool louvain_trace() {
-  // MGX_LOUVAIN_TRACE: bare stderr phase markers with NO syncs and NO
-  // allocations — under AMD_SERIALIZE_KERNEL the process aborts inside the
-  // faulting launch, so the last marker identifies the kernel without
-  // perturbing timing or the allocation layout (the full DEBUG mode's
-  // extra buffers/syncs mask the storm fault — r02 finding).
-  static const bool v = [] {
-    const char *e = getenv("MGX_LOUVAIN_TRACE");
-    return e && atoi(e) != 0;
-  }();
-  return v;
-}
-
-#define MGX_LTRACE(...)                                                       \
-  do {                                                                        \
-    if (louvain_trace()) {                                                    \
-      fprintf(stderr, "[ltrace] " __VA_ARGS__);                               \
-      fprintf(stderr, "\n");                                                  \
-      fflush(stderr);                                                         \
-    }                                                                         \
-  } while (0)
-
-inline int louvain_diag(const char *name) {
-  // diagnostic-only switches for the storm-fault bisect (r02):
-  //   MGX_LOUVAIN_SKIP_SMALL / _SKIP_BIG: omit a sweep kernel (results
-  //   WRONG — bisect only), MGX_LOUVAIN_SYNC_AFTER: sync+getLastError
-  //   after each sweep launch and print the status.
-  const char *e = getenv(name);
-  return e && atoi(e) != 0;
-}
-
-inline bool louvain_debug() {
-  static const bool v = [] {
-    const char *e = getenv("MGX_LOUVAIN_DEBUG");
-    return e && atoi(e) != 0;
-  }();
-  return v;
-}
-
-#define MGX_LDBG(ctx, ...)                                                    \
-  do {                                                                        \
-    if (louvain_debug()) {                                                    \
-      hipError_t _se = hipStreamSynchronize((ctx)->stream);                   \
-      hipError_t _ke = hipGetLastError();                                     \
-      fprintf(stderr, "[louvain] " __VA_ARGS__);                              \
-      fprintf(stderr, " sync=%s last=%s\n", hipGetErrorString(_se),          \
-              hipGetErrorString(_ke));                                        \
-      fflush(stderr);                                                         \
-    }                                                                         \
-  } while (0)
-
 struct Level {
   int64_t nv = 0;
   uint32_t *row_ptr = nullptr;  // [nv+1]
   int32_t *col = nullptr;       // [ne2]
   double *w = nullptr;          // [ne2]
   int64_t ne2 = 0;              // entries (each input edge twice)
-  bool arena = false;           // col/w live in ctx->louv_* (not freed here)
+};
+
+// Rows with edges, split at kSmallRowDeg; built once per level (k_fill_rows).
+struct RowLists {
+  int32_t *small = nullptr;
+  int64_t n_small = 0;
+  int32_t *big = nullptr;
+  int64_t n_big = 0;
 };
 
 // ---------- generic small kernels ----------------------------------------
-
-__global__ void k_f32_to_f64(int64_t n, const float *in, double *out) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    out[i] = (double)in[i];
-}
 
 // sumVertexDegree (utilityClusteringFunctions.cpp:68-85), wave-per-row over
 // the small list and block-per-row over the big list (a thread-per-row scan
@@ -140,22 +91,18 @@ __global__ void k_row_wsum_small(int64_t n_small, const int32_t *small_rows,
 __global__ void __launch_bounds__(kBlock) k_row_wsum_big(
     int64_t n_big, const int32_t *big_rows, const uint32_t *row_ptr, const double *w,
     double *vdeg, double *cinfo_deg) {
-  __shared__ double red[kBlock / 64];
-  for (int64_t bi = blockIdx.x; bi < n_big; bi += gridDim.x) {
-    const int32_t row = big_rows[bi];
-    double acc = 0.0;
-    for (uint32_t j = row_ptr[row] + threadIdx.x; j < row_ptr[row + 1]; j += kBlock)
-      acc += w[j];
-    for (int o = 32; o; o >>= 1) acc += __shfl_down(acc, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double t = red[0] + red[1] + red[2] + red[3];
-      vdeg[row] = t;
-      cinfo_deg[row] = t;
-    }
-    __syncthreads();
-  }
+  // Block per big row; row_reduce<256> adds the four wave sums left to right.
+  reduce_rows<kBlock>(
+      big_rows, n_big, blockIdx.x, gridDim.x, 0.0, mgx_op_add(),
+      [&](int32_t row, int sub) {
+        double acc = 0.0;
+        for (uint32_t j = row_ptr[row] + sub; j < row_ptr[row + 1]; j += kBlock) acc += w[j];
+        return acc;
+      },
+      [&](int32_t row, double t) {
+        vdeg[row] = t;
+        cinfo_deg[row] = t;
+      });
 }
 
 __global__ void k_sum_f64(int64_t n, const double *x, double *out) {
@@ -191,14 +138,16 @@ struct SweepArgs {
   const uint32_t *row_ptr;
   const int32_t *col;
   const double *w;
-  const double *vdeg;
-  const double *cinfo_deg;
-  const int32_t *cinfo_size;
+  double *vdeg;
+  double *cinfo_deg;
+  int32_t *cinfo_size;
   const int32_t *curr;
   int32_t *target;
   double *cupd_deg;
   int32_t *cupd_size;
-  double *e_xx;  // += Counter[0] per vertex (clusterWeightInternal sum)
+  // [e_xx, a2_x, total_w]; the sweeps add Counter[0] per vertex into e_xx
+  // (clusterWeightInternal sum)
+  double *e_xx;
   double constant;
   // work lists
   const int32_t *small_rows;
@@ -210,11 +159,7 @@ struct SweepArgs {
   double *pool_vals;
   const uint64_t *pool_off;  // [n_big+1]
   uint64_t pool_total;
-  int inkernel_clear;        // experiment flag (MGX_LOUVAIN_INKERNEL_CLEAR)
   int64_t nv;                // level vertex count (community-id bound)
-  int diag_mask;             // storm-bisect arms (MGX_LOUVAIN_DIAG bitmask):
-                             // 1: no cupd atomics, 2: no e_xx add,
-                             // 4: targets forced to stay (sc)
   // Always-on guard accounting (4 u32 slots, device):
   //   [0] region-invariant violation bits (big-row pool geometry)
   //   [1] out-of-range max_index count (the suspected OOB vector of the
@@ -235,14 +180,6 @@ __device__ inline int32_t guard_max_index(const SweepArgs &A, int32_t max_index,
   return max_index;
 }
 
-__device__ inline void wave_lds_fence() {
-  // Wave-level LDS completion + compiler ordering: the per-wave hash table
-  // region is touched only by this wave's 64 lanes, so draining lgkmcnt
-  // after the write phase makes every lane's LDS writes visible to every
-  // lane's subsequent reads (no cross-wave traffic => no s_barrier needed).
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-}
-
 __device__ inline double dq_gain(double eiy, double eix, double vdeg_i, double ay,
                                  double ax, double constant) {
   return 2.0 * (eiy - eix) - 2.0 * vdeg_i * (ay - ax) * constant;
@@ -255,12 +192,47 @@ struct Best {
   int32_t cid;
 };
 
+// a beats b: strictly larger gain, or equal non-zero gain and smaller id.
+__device__ inline bool better(Best a, Best b) {
+  return a.gain > b.gain || (a.gain == b.gain && a.gain != 0.0 && a.cid < b.cid);
+}
+
+// The wave's best, valid in lane 0.
+__device__ inline Best wave_best(Best best) {
+  for (int o = 32; o; o >>= 1) {
+    const Best other{__shfl_down(best.gain, o, 64), __shfl_down(best.cid, o, 64)};
+    if (better(other, best)) best = other;
+  }
+  return best;
+}
+
+// One lane per row: adopt the row's best move into target and the community
+// update deltas; `own` is the row's weight into its own community sc.
+__device__ inline void commit_move(const SweepArgs &A, int32_t row, int32_t sc, Best best,
+                                   double own) {
+  int32_t max_index = guard_max_index(A, (best.gain > 0.0) ? best.cid : sc, sc, row);
+  // swap protection (max(), utilityClusteringFunctions.cpp:305-307)
+  if (A.cinfo_size[max_index] == 1 && A.cinfo_size[sc] == 1 && max_index > sc)
+    max_index = sc;
+  A.target[row] = max_index;
+  if (max_index != sc) {
+    atomicAdd(&A.cupd_deg[max_index], A.vdeg[row]);
+    atomicAdd(&A.cupd_size[max_index], 1);
+    atomicAdd(&A.cupd_deg[sc], -A.vdeg[row]);
+    atomicAdd(&A.cupd_size[sc], -1);
+  }
+  atomicAdd(A.e_xx, own);
+}
+
 // One wave processes one small row using its LDS table region.
 __global__ void __launch_bounds__(kBlock) k_sweep_small(SweepArgs A) {
-  __shared__ int32_t keys[kBlock / 64][kLdsCap];
-  __shared__ double vals[kBlock / 64][kLdsCap];
+  __shared__ int32_t s_keys[kBlock / 64][kLdsCap];
+  __shared__ double s_vals[kBlock / 64][kLdsCap];
+  constexpr uint32_t mask = kLdsCap - 1;
   const int wave = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
+  int32_t *keys = s_keys[wave];
+  double *vals = s_vals[wave];
   const int64_t waves_per_grid = (int64_t)gridDim.x * (kBlock / 64);
   for (int64_t wi = (int64_t)blockIdx.x * (kBlock / 64) + wave; wi < A.n_small;
        wi += waves_per_grid) {
@@ -269,83 +241,47 @@ __global__ void __launch_bounds__(kBlock) k_sweep_small(SweepArgs A) {
     const int32_t sc = A.curr[row];
     // clear table
     for (int s = lane; s < kLdsCap; s += 64) {
-      keys[wave][s] = -1;
-      vals[wave][s] = 0.0;
+      keys[s] = -1;
+      vals[s] = 0.0;
     }
     wave_lds_fence();
-    // seed own community (buildLocalMapCounter seeds Counter[0]=0)
-    if (lane == 0) {
-      uint32_t h = ((uint32_t)sc * 2654435761u) & (kLdsCap - 1);
-      keys[wave][h] = sc;  // first insert, empty table: no probe needed
-    }
+    // seed own community (buildLocalMapCounter seeds Counter[0]=0); first
+    // insert into an empty table: no probe needed
+    if (lane == 0) keys[comm_slot(sc, mask)] = sc;
     wave_lds_fence();
     double self_loop = 0.0;
     for (uint32_t j = adj1 + lane; j < adj2; j += 64) {
       const int32_t nb = A.col[j];
       const double wj = A.w[j];
       if (nb == row) self_loop += wj;
-      const int32_t cid = A.curr[nb];
-      uint32_t h = ((uint32_t)cid * 2654435761u) & (kLdsCap - 1);
-      while (true) {
-        int32_t prev = atomicCAS(&keys[wave][h], -1, cid);
-        if (prev == -1 || prev == cid) break;
-        h = (h + 1) & (kLdsCap - 1);
-      }
-      atomicAdd(&vals[wave][h], wj);
+      comm_add(keys, vals, mask, A.curr[nb], wj);
     }
     for (int o = 32; o; o >>= 1) self_loop += __shfl_down(self_loop, o, 64);
     self_loop = __shfl(self_loop, 0, 64);
     wave_lds_fence();
-    // lookup own bucket
-    double own = 0.0;
-    {
-      uint32_t h = ((uint32_t)sc * 2654435761u) & (kLdsCap - 1);
-      int probes = 0;
-      while (keys[wave][h] != sc && ++probes <= kLdsCap) h = (h + 1) & (kLdsCap - 1);
-      if (probes > kLdsCap) {
-        atomicOr(&A.guard[0], 16u);  // own-community entry vanished from LDS
-      } else {
-        own = vals[wave][h];
-      }
-    }
+    bool found;
+    const double own = comm_find<false>(keys, vals, mask, kLdsCap, sc, &found);
+    if (!found) atomicOr(&A.guard[0], 16u);  // own-community entry vanished from LDS
     const double eix = own - self_loop;
     const double ax = A.cinfo_deg[sc] - A.vdeg[row];
     Best best{0.0, sc};
     for (int s = lane; s < kLdsCap; s += 64) {
-      const int32_t cid = keys[wave][s];
+      const int32_t cid = keys[s];
       if (cid >= 0 && cid != sc) {
-        const double gain =
-            dq_gain(vals[wave][s], eix, A.vdeg[row], A.cinfo_deg[cid], ax, A.constant);
-        if (gain > best.gain || (gain == best.gain && gain != 0.0 && cid < best.cid))
-          best = Best{gain, cid};
+        const Best cand{
+            dq_gain(vals[s], eix, A.vdeg[row], A.cinfo_deg[cid], ax, A.constant), cid};
+        if (better(cand, best)) best = cand;
       }
     }
-    for (int o = 32; o; o >>= 1) {
-      Best other{__shfl_down(best.gain, o, 64), __shfl_down(best.cid, o, 64)};
-      if (other.gain > best.gain ||
-          (other.gain == best.gain && other.gain != 0.0 && other.cid < best.cid))
-        best = other;
-    }
-    if (lane == 0) {
-      int32_t max_index = guard_max_index(A, (best.gain > 0.0) ? best.cid : sc, sc, row);
-      // swap protection (max(), utilityClusteringFunctions.cpp:305-307)
-      if (A.cinfo_size[max_index] == 1 && A.cinfo_size[sc] == 1 && max_index > sc)
-        max_index = sc;
-      if (A.diag_mask & 4) max_index = sc;
-      A.target[row] = max_index;
-      if (max_index != sc && !(A.diag_mask & 1)) {
-        atomicAdd(&A.cupd_deg[max_index], A.vdeg[row]);
-        atomicAdd(&A.cupd_size[max_index], 1);
-        atomicAdd(&A.cupd_deg[sc], -A.vdeg[row]);
-        atomicAdd(&A.cupd_size[sc], -1);
-      }
-      if (!(A.diag_mask & 2)) atomicAdd(A.e_xx, own);
-    }
+    best = wave_best(best);
+    if (lane == 0) commit_move(A, row, sc, best, own);
     wave_lds_fence();
   }
 }
 
-// One 256-thread block per big row, table region in the global pool.
+// One 256-thread block per big row, table region in the global pool (cleared
+// before the launch: a per-row clear in here was implicated in memory faults
+// at RMAT-24; see git history).
 __global__ void __launch_bounds__(kBlock) k_sweep_big(SweepArgs A) {
   __shared__ double s_red[kBlock / 64];
   __shared__ int32_t s_cid[kBlock / 64];
@@ -355,27 +291,15 @@ __global__ void __launch_bounds__(kBlock) k_sweep_big(SweepArgs A) {
     const int32_t sc = A.curr[row];
     const uint64_t t0 = A.pool_off[bi], t1 = A.pool_off[bi + 1];
     const uint32_t cap = (uint32_t)(t1 - t0);  // power of two
+    const uint32_t mask = cap - 1;
     int32_t *keys = A.pool_keys + t0;
     double *vals = A.pool_vals + t0;
-    // Region invariants (diagnosing the in-kernel-clear fault): offsets
-    // monotone, power-of-two capacity, region within the pool.
     if (threadIdx.x == 0) {
-      if (t1 <= t0 || t1 > A.pool_total || (cap & (cap - 1)) != 0 ||
-          cap < 2 * (adj2 - adj1))
+      // Region invariants: offsets monotone, power-of-two capacity, region
+      // within the pool.
+      if (t1 <= t0 || t1 > A.pool_total || (cap & mask) != 0 || cap < 2 * (adj2 - adj1))
         atomicOr(&A.guard[0], 1u);
-    }
-    if (A.inkernel_clear) {
-      for (uint32_t sIdx = threadIdx.x; sIdx < cap; sIdx += kBlock) {
-        keys[sIdx] = -1;
-        vals[sIdx] = 0.0;
-      }
-      __syncthreads();
-    }
-    // Otherwise the pool is cleared before the launch (the in-kernel
-    // variant was implicated in memory faults at RMAT-24; see git history).
-    if (threadIdx.x == 0) {
-      uint32_t h = ((uint32_t)sc * 2654435761u) & (cap - 1);
-      keys[h] = sc;
+      keys[comm_slot(sc, mask)] = sc;
     }
     __syncthreads();
     double self_loop = 0.0;
@@ -383,14 +307,7 @@ __global__ void __launch_bounds__(kBlock) k_sweep_big(SweepArgs A) {
       const int32_t nb = A.col[j];
       const double wj = A.w[j];
       if (nb == row) self_loop += wj;
-      const int32_t cid = A.curr[nb];
-      uint32_t h = ((uint32_t)cid * 2654435761u) & (cap - 1);
-      while (true) {
-        int32_t prev = atomicCAS(&keys[h], -1, cid);
-        if (prev == -1 || prev == cid) break;
-        h = (h + 1) & (cap - 1);
-      }
-      atomicAdd(&vals[h], wj);
+      comm_add(keys, vals, mask, A.curr[nb], wj);
     }
     // block sum of self_loop
     for (int o = 32; o; o >>= 1) self_loop += __shfl_down(self_loop, o, 64);
@@ -398,35 +315,21 @@ __global__ void __launch_bounds__(kBlock) k_sweep_big(SweepArgs A) {
     __syncthreads();
     double sl = s_red[0] + s_red[1] + s_red[2] + s_red[3];
     __syncthreads();
-    double own = 0.0;
-    {
-      uint32_t h = ((uint32_t)sc * 2654435761u) & (cap - 1);
-      uint32_t probes = 0;
-      while (keys[h] != sc && ++probes <= cap) h = (h + 1) & (cap - 1);
-      if (probes > cap) {
-        atomicOr(&A.guard[0], 32u);  // own-community entry vanished from pool
-      } else {
-        own = vals[h];
-      }
-    }
+    bool found;
+    const double own = comm_find<false>(keys, vals, mask, cap, sc, &found);
+    if (!found) atomicOr(&A.guard[0], 32u);  // own-community entry vanished from pool
     const double eix = own - sl;
     const double ax = A.cinfo_deg[sc] - A.vdeg[row];
     Best best{0.0, sc};
     for (uint32_t s = threadIdx.x; s < cap; s += kBlock) {
       const int32_t cid = keys[s];
       if (cid >= 0 && cid != sc) {
-        const double gain =
-            dq_gain(vals[s], eix, A.vdeg[row], A.cinfo_deg[cid], ax, A.constant);
-        if (gain > best.gain || (gain == best.gain && gain != 0.0 && cid < best.cid))
-          best = Best{gain, cid};
+        const Best cand{
+            dq_gain(vals[s], eix, A.vdeg[row], A.cinfo_deg[cid], ax, A.constant), cid};
+        if (better(cand, best)) best = cand;
       }
     }
-    for (int o = 32; o; o >>= 1) {
-      Best other{__shfl_down(best.gain, o, 64), __shfl_down(best.cid, o, 64)};
-      if (other.gain > best.gain ||
-          (other.gain == best.gain && other.gain != 0.0 && other.cid < best.cid))
-        best = other;
-    }
+    best = wave_best(best);
     if ((threadIdx.x & 63) == 0) {
       s_red[threadIdx.x >> 6] = best.gain;
       s_cid[threadIdx.x >> 6] = best.cid;
@@ -434,22 +337,10 @@ __global__ void __launch_bounds__(kBlock) k_sweep_big(SweepArgs A) {
     __syncthreads();
     if (threadIdx.x == 0) {
       for (int i = 1; i < kBlock / 64; ++i) {
-        Best other{s_red[i], s_cid[i]};
-        if (other.gain > best.gain ||
-            (other.gain == best.gain && other.gain != 0.0 && other.cid < best.cid))
-          best = other;
+        const Best other{s_red[i], s_cid[i]};
+        if (better(other, best)) best = other;
       }
-      int32_t max_index = guard_max_index(A, (best.gain > 0.0) ? best.cid : sc, sc, row);
-      if (A.cinfo_size[max_index] == 1 && A.cinfo_size[sc] == 1 && max_index > sc)
-        max_index = sc;
-      A.target[row] = max_index;
-      if (max_index != sc) {
-        atomicAdd(&A.cupd_deg[max_index], A.vdeg[row]);
-        atomicAdd(&A.cupd_size[max_index], 1);
-        atomicAdd(&A.cupd_deg[sc], -A.vdeg[row]);
-        atomicAdd(&A.cupd_size[sc], -1);
-      }
-      atomicAdd(A.e_xx, own);
+      commit_move(A, row, sc, best, own);
     }
     __syncthreads();
   }
@@ -470,6 +361,17 @@ __global__ void k_rep_min(int64_t nv, const int32_t *C, int32_t *rep) {
        i += (int64_t)gridDim.x * blockDim.x) {
     if (C[i] >= 0) atomicMin(&rep[C[i]], (int32_t)i);
   }
+}
+
+// Active communities = sorted reps below INT32_MAX.
+__global__ void k_count_active(int64_t n, const uint32_t *sorted_rep,
+                               unsigned long long *out) {
+  unsigned long long acc = 0;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x)
+    if (sorted_rep[i] != 0x7FFFFFFFu) ++acc;
+  block_reduce_atomic(acc, 0ull, mgx_op_add(),
+                      [&](unsigned long long s) { atomicAdd(out, s); });
 }
 
 __global__ void k_newid_from_sorted(int64_t n_active, const int32_t *sorted_c,
@@ -523,21 +425,6 @@ __global__ void k_row_of_entry_big(int64_t n_big, const int32_t *rows,
     for (uint32_t j = row_ptr[row] + threadIdx.x; j < row_ptr[row + 1]; j += kBlock)
       row_of_entry[j] = row;
   }
-}
-
-// diagnostic: count non-sentinel keys with components outside [0, ncl)
-__global__ void k_validate_keys(int64_t n, const uint64_t *keys, int64_t ncl,
-                                uint64_t sentinel, unsigned long long *bad) {
-  unsigned long long acc = 0;
-  for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n;
-       k += (int64_t)gridDim.x * blockDim.x) {
-    const uint64_t key = keys[k];
-    if (key == sentinel) continue;
-    const int64_t ci = (int64_t)(key >> 32);
-    const int64_t ct = (int64_t)(uint32_t)key;
-    if (ci < 0 || ci >= ncl || ct < 0 || ct >= ncl) ++acc;
-  }
-  if (acc) atomicAdd(bad, acc);
 }
 
 // count CSR rows for unique pairs (ci>=ct): row ci +1; if ct<ci also row ct +1.
@@ -664,734 +551,476 @@ __global__ void k_fill_rows(int64_t nv, const uint32_t *row_ptr, int32_t *small_
   }
 }
 
-__global__ void k_check_lists(int64_t nv, const uint32_t *row_ptr, const int32_t *small_rows,
-                              int64_t n_small, const int32_t *big_rows, int64_t n_big,
-                              uint32_t *mark, uint32_t *err) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n_small + n_big;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const int32_t row = i < n_small ? small_rows[i] : big_rows[i - n_small];
-    if (row < 0 || row >= nv) {
-      atomicOr(err, 1u);
-      continue;
-    }
-    atomicAdd(&mark[row], 1u);
-    const uint32_t deg = row_ptr[row + 1] - row_ptr[row];
-    if (i < n_small && !(deg > 0 && deg < kSmallRowDeg)) atomicOr(err, 2u);
-    if (i >= n_small && deg < kSmallRowDeg) atomicOr(err, 4u);
-  }
-}
-
-__global__ void k_check_marks(int64_t nv, const uint32_t *row_ptr, const uint32_t *mark,
-                              uint32_t *err) {
-  for (int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; v < nv;
-       v += (int64_t)gridDim.x * blockDim.x) {
-    const uint32_t deg = row_ptr[v + 1] - row_ptr[v];
-    const uint32_t expect = deg > 0 ? 1u : 0u;
-    if (mark[v] != expect) atomicOr(err, 8u);
-  }
-}
-
 // ---------- host orchestration -------------------------------------------
 
-struct DevBuf {
-  // Allocation from the context's caching free list (mgx_internal.h): the
-  // per-level multi-GB hipMalloc/hipFree pairs cost ~2 s of host time per
-  // Louvain call at RMAT-24 (measured); the cache pays it once per process.
-  mgx_context *ctx = nullptr;
-  void *p = nullptr;
-  ~DevBuf() {
-    if (p) (void)ctx->free_async(p);
-  }
-  hipError_t alloc(mgx_context *c, size_t bytes) {
-    ctx = c;
-    return c->alloc_async(&p, bytes) == MGX_OK ? hipSuccess : hipErrorOutOfMemory;
-  }
-  template <typename T>
-  T *as() {
-    return (T *)p;
-  }
-};
-
-mgx_status read_scalar_f64(mgx_context *ctx, const double *d, double *out) {
-  MGX_HIP_TRY(hipMemcpyAsync(out, d, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+// n values from the device, synchronized.
+template <typename T>
+mgx_status read_back(mgx_context *ctx, const T *d, T *out, int64_t n = 1) {
+  MGX_HIP_TRY(hipMemcpyAsync(out, d, n * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
   MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
   return MGX_OK;
 }
 
-// Runs parallelLouvianMethod on one level. C (device i32[nv]) receives
-// pastCommAss. Returns modularity via *out_mod.
-mgx_status louvain_level(mgx_context *ctx, const Level &L, double lower, double thresh,
-                         int32_t *C, double *out_mod, int64_t *iters_out) {
-  const int64_t nv = L.nv;
-  DevBuf vdeg, cinfo_deg, cinfo_size, cupd_deg, cupd_size, past, curr, target, scalars;
-  MGX_HIP_TRY(vdeg.alloc(ctx, nv * 8));
-  MGX_HIP_TRY(cinfo_deg.alloc(ctx, nv * 8));
-  MGX_HIP_TRY(cinfo_size.alloc(ctx, nv * 4));
-  MGX_HIP_TRY(cupd_deg.alloc(ctx, nv * 8));
-  MGX_HIP_TRY(cupd_size.alloc(ctx, nv * 4));
-  MGX_HIP_TRY(past.alloc(ctx, nv * 4));
-  MGX_HIP_TRY(curr.alloc(ctx, nv * 4));
-  MGX_HIP_TRY(target.alloc(ctx, nv * 4));
-  MGX_HIP_TRY(scalars.alloc(ctx, 3 * 8));  // [e_xx, a2_x, total_w]
+// MGX_LOUVAIN_STRICT=1: a guard that fired fails the call instead of only
+// reporting on stderr.
+bool louvain_strict() {
+  const char *e = getenv("MGX_LOUVAIN_STRICT");
+  return e && atoi(e) != 0;
+}
 
-  MGX_HIP_TRY(hipMemsetAsync(scalars.as<double>() + 2, 0, 8, ctx->stream));
-  hipLaunchKernelGGL(mgx_k_iota<int32_t>, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0,
-                     ctx->stream, nv, past.as<int32_t>());
-  hipLaunchKernelGGL(mgx_k_iota<int32_t>, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0,
-                     ctx->stream, nv, curr.as<int32_t>());
-  MGX_HIP_TRY(hipMemsetAsync(cupd_deg.p, 0, nv * 8, ctx->stream));
-  MGX_HIP_TRY(hipMemsetAsync(cupd_size.p, 0, nv * 4, ctx->stream));
-
-  // Row classification + big-row pool.
-  DevBuf counters, small_rows, big_rows, pool_off, pool_keys, pool_vals;
-  MGX_HIP_TRY(counters.alloc(ctx, 4 * 4));
-  MGX_HIP_TRY(hipMemsetAsync(counters.p, 0, 16, ctx->stream));
-  hipLaunchKernelGGL(k_classify_rows, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0,
-                     ctx->stream, nv, L.row_ptr, counters.as<uint32_t>(),
-                     counters.as<uint32_t>() + 1);
+// The level's row lists, in the caller's scope.
+mgx_status build_row_lists(mgx_scope &own, const Level &L, RowLists *R) {
+  mgx_context *ctx = own.ctx;
+  mgx_scope bufs(ctx);
+  uint32_t *counters = nullptr;  // [n_small, n_big]
+  MGX_TRY(bufs.alloc(&counters, 4));
+  MGX_HIP_TRY(hipMemsetAsync(counters, 0, 16, ctx->stream));
+  hipLaunchKernelGGL(k_classify_rows, dim3((uint32_t)grid_for(L.nv)), dim3(kBlock), 0,
+                     ctx->stream, L.nv, L.row_ptr, counters, counters + 1);
   uint32_t h_counts[2] = {0, 0};
-  MGX_HIP_TRY(hipMemcpyAsync(h_counts, counters.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-  MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  const int64_t n_small = h_counts[0], n_big = h_counts[1];
-  MGX_HIP_TRY(small_rows.alloc(ctx, n_small * 4));
-  MGX_HIP_TRY(big_rows.alloc(ctx, n_big * 4));
-  MGX_HIP_TRY(hipMemsetAsync(counters.p, 0, 16, ctx->stream));
-  hipLaunchKernelGGL(k_fill_rows, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0,
-                     ctx->stream, nv, L.row_ptr, small_rows.as<int32_t>(),
-                     big_rows.as<int32_t>(), counters.as<uint32_t>(),
-                     counters.as<uint32_t>() + 1);
-  if (louvain_debug()) {
-    DevBuf mark, errbuf;
-    MGX_HIP_TRY(mark.alloc(ctx, nv * 4));
-    MGX_HIP_TRY(errbuf.alloc(ctx, 4));
-    MGX_HIP_TRY(hipMemsetAsync(mark.p, 0, nv * 4, ctx->stream));
-    MGX_HIP_TRY(hipMemsetAsync(errbuf.p, 0, 4, ctx->stream));
-    hipLaunchKernelGGL(k_check_lists, dim3((uint32_t)grid_for(n_small + n_big)),
-                       dim3(kBlock), 0, ctx->stream, nv, L.row_ptr,
-                       small_rows.as<int32_t>(), n_small, big_rows.as<int32_t>(), n_big,
-                       mark.as<uint32_t>(), errbuf.as<uint32_t>());
-    hipLaunchKernelGGL(k_check_marks, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0,
-                       ctx->stream, nv, L.row_ptr, mark.as<uint32_t>(),
-                       errbuf.as<uint32_t>());
-    uint32_t e = 0;
-    MGX_HIP_TRY(hipMemcpyAsync(&e, errbuf.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-    MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    fprintf(stderr, "[louvain] LIST CHECK nv=%lld err=%u\n", (long long)nv, e);
-    fflush(stderr);
-  }
-  // Binned row weight sums (sumVertexDegree) over the just-built lists.
-  MGX_LTRACE("setup k_row_wsum_init nv=%lld", (long long)nv);
-  hipLaunchKernelGGL(k_row_wsum_init, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0,
-                     ctx->stream, nv, vdeg.as<double>(), cinfo_deg.as<double>(),
-                     cinfo_size.as<int32_t>());
-  if (n_small > 0)
-    hipLaunchKernelGGL(k_row_wsum_small, dim3((uint32_t)grid_for(n_small)), dim3(kBlock),
-                       0, ctx->stream, n_small, small_rows.as<int32_t>(), L.row_ptr, L.w,
-                       vdeg.as<double>(), cinfo_deg.as<double>());
-  if (n_big > 0)
-    hipLaunchKernelGGL(k_row_wsum_big, dim3((uint32_t)(n_big < 4096 ? n_big : 4096)),
-                       dim3(kBlock), 0, ctx->stream, n_big, big_rows.as<int32_t>(),
-                       L.row_ptr, L.w, vdeg.as<double>(), cinfo_deg.as<double>());
-  hipLaunchKernelGGL(k_sum_f64, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0, ctx->stream,
-                     nv, vdeg.as<double>(), scalars.as<double>() + 2);
-  double total_w = 0.0;
-  MGX_TRY(read_scalar_f64(ctx, scalars.as<double>() + 2, &total_w));
-  const double constant = 1.0 / total_w;  // calConstantForSecondTerm
+  MGX_TRY(read_back(ctx, counters, h_counts, 2));
+  R->n_small = h_counts[0];
+  R->n_big = h_counts[1];
+  MGX_TRY(own.alloc(&R->small, R->n_small));
+  MGX_TRY(own.alloc(&R->big, R->n_big));
+  MGX_HIP_TRY(hipMemsetAsync(counters, 0, 16, ctx->stream));
+  hipLaunchKernelGGL(k_fill_rows, dim3((uint32_t)grid_for(L.nv)), dim3(kBlock), 0,
+                     ctx->stream, L.nv, L.row_ptr, R->small, R->big, counters, counters + 1);
+  return MGX_OK;
+}
 
-  MGX_LDBG(ctx, "level nv=%lld n_small=%lld n_big=%lld wsum done", (long long)nv,
-           (long long)n_small, (long long)n_big);
-  uint64_t pool_total = 0;
-  if (n_big > 0) {
-    DevBuf caps;
-    MGX_HIP_TRY(caps.alloc(ctx, n_big * 8));
-    hipLaunchKernelGGL(k_big_caps, dim3((uint32_t)grid_for(n_big)), dim3(kBlock), 0,
-                       ctx->stream, n_big, big_rows.as<int32_t>(), L.row_ptr,
-                       caps.as<uint64_t>());
-    MGX_HIP_TRY(pool_off.alloc(ctx, (n_big + 1) * 8));
-    MGX_TRY(mgx_with_temp(ctx, "louvain pool scan", [&](void *tmp, size_t &bytes) {
-      return rocprim::exclusive_scan(tmp, bytes, caps.as<uint64_t>(), pool_off.as<uint64_t>(),
-                                     (uint64_t)0, n_big, rocprim::plus<uint64_t>(),
-                                     ctx->stream);
-    }));
-    uint64_t last_off = 0, last_cap = 0;
-    MGX_HIP_TRY(hipMemcpyAsync(&last_off, pool_off.as<uint64_t>() + n_big - 1, 8,
-                               hipMemcpyDeviceToHost, ctx->stream));
-    MGX_HIP_TRY(hipMemcpyAsync(&last_cap, caps.as<uint64_t>() + n_big - 1, 8,
-                               hipMemcpyDeviceToHost, ctx->stream));
-    MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    pool_total = last_off + last_cap;
-    MGX_HIP_TRY(hipMemcpyAsync(pool_off.as<uint64_t>() + n_big, &pool_total, 8,
-                               hipMemcpyHostToDevice, ctx->stream));
-    MGX_HIP_TRY(pool_keys.alloc(ctx, pool_total * 4));
-    MGX_HIP_TRY(pool_vals.alloc(ctx, pool_total * 8));
-  }
-
-  MGX_LDBG(ctx, "pool_total=%llu", (unsigned long long)pool_total);
-  MGX_LTRACE("setup done pool_total=%llu n_small=%lld n_big=%lld",
-             (unsigned long long)pool_total, (long long)n_small, (long long)n_big);
-  SweepArgs A;
-  A.row_ptr = L.row_ptr;
-  A.col = L.col;
-  A.w = L.w;
-  A.vdeg = vdeg.as<double>();
-  A.cinfo_deg = cinfo_deg.as<double>();
-  A.cinfo_size = cinfo_size.as<int32_t>();
-  A.cupd_deg = cupd_deg.as<double>();
-  A.cupd_size = cupd_size.as<int32_t>();
-  A.e_xx = scalars.as<double>();
-  A.constant = constant;
-  A.small_rows = small_rows.as<int32_t>();
-  A.n_small = n_small;
-  A.big_rows = big_rows.as<int32_t>();
-  A.n_big = n_big;
-  A.pool_keys = pool_keys.as<int32_t>();
-  A.pool_vals = pool_vals.as<double>();
-  A.pool_off = pool_off.as<uint64_t>();
-  A.pool_total = pool_total;
-  A.inkernel_clear = 0;
-  A.nv = nv;
-  {
-    const char *e = getenv("MGX_LOUVAIN_DIAG");
-    A.diag_mask = e ? atoi(e) : 0;
-  }
-  DevBuf guard;
-  {
-    const char *e = getenv("MGX_LOUVAIN_INKERNEL_CLEAR");
-    if (e && atoi(e)) A.inkernel_clear = 1;
-  }
+// State init and weight sums: the level's vertex and community arrays (in
+// `own`), singleton communities, sumVertexDegree binned over the row lists,
+// calConstantForSecondTerm.
+mgx_status init_level_state(mgx_scope &own, const Level &L, const RowLists &R,
+                            SweepArgs *A) {
+  mgx_context *ctx = own.ctx;
+  const int64_t nv = L.nv;
+  A->row_ptr = L.row_ptr;
+  A->col = L.col;
+  A->w = L.w;
+  A->nv = nv;
+  A->small_rows = R.small;
+  A->n_small = R.n_small;
+  A->big_rows = R.big;
+  A->n_big = R.n_big;
+  MGX_TRY(own.alloc(&A->vdeg, nv));
+  MGX_TRY(own.alloc(&A->cinfo_deg, nv));
+  MGX_TRY(own.alloc(&A->cinfo_size, nv));
+  MGX_TRY(own.alloc(&A->cupd_deg, nv));
+  MGX_TRY(own.alloc(&A->cupd_size, nv));
+  MGX_TRY(own.alloc(&A->e_xx, 3));
   // Guard accounting is ALWAYS on (cost: one 16-B buffer + one lane-0 branch
   // per row — unmeasurable next to the sweep's hash traffic).
-  MGX_HIP_TRY(guard.alloc(ctx, 16));
-  {
-    static const uint32_t init[4] = {0u, 0u, 0xFFFFFFFFu, 0xFFFFFFFFu};
-    MGX_HIP_TRY(hipMemcpyAsync(guard.p, init, 16, hipMemcpyHostToDevice, ctx->stream));
-  }
-  A.guard = guard.as<uint32_t>();
+  MGX_TRY(own.alloc(&A->guard, 4));
+  static const uint32_t guard_init[4] = {0u, 0u, 0xFFFFFFFFu, 0xFFFFFFFFu};
+  MGX_HIP_TRY(hipMemcpyAsync(A->guard, guard_init, 16, hipMemcpyHostToDevice, ctx->stream));
+  MGX_HIP_TRY(hipMemsetAsync(A->e_xx + 2, 0, 8, ctx->stream));
+  MGX_HIP_TRY(hipMemsetAsync(A->cupd_deg, 0, nv * 8, ctx->stream));
+  MGX_HIP_TRY(hipMemsetAsync(A->cupd_size, 0, nv * 4, ctx->stream));
+  hipLaunchKernelGGL(k_row_wsum_init, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0,
+                     ctx->stream, nv, A->vdeg, A->cinfo_deg, A->cinfo_size);
+  if (R.n_small > 0)
+    hipLaunchKernelGGL(k_row_wsum_small, dim3((uint32_t)grid_for(R.n_small)), dim3(kBlock),
+                       0, ctx->stream, R.n_small, R.small, L.row_ptr, L.w, A->vdeg,
+                       A->cinfo_deg);
+  if (R.n_big > 0)
+    hipLaunchKernelGGL(k_row_wsum_big, dim3((uint32_t)(R.n_big < 4096 ? R.n_big : 4096)),
+                       dim3(kBlock), 0, ctx->stream, R.n_big, R.big, L.row_ptr, L.w, A->vdeg,
+                       A->cinfo_deg);
+  hipLaunchKernelGGL(k_sum_f64, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0, ctx->stream,
+                     nv, A->vdeg, A->e_xx + 2);
+  double total_w = 0.0;
+  MGX_TRY(read_back(ctx, A->e_xx + 2, &total_w));
+  A->constant = 1.0 / total_w;  // calConstantForSecondTerm
+  return MGX_OK;
+}
 
-  double prev_mod = -1.0, curr_mod = -1.0;
+// Hub pool sizing: one power-of-two table region per big row, in `own`.
+mgx_status size_hub_pool(mgx_scope &own, SweepArgs *A) {
+  mgx_context *ctx = own.ctx;
+  const int64_t n_big = A->n_big;
+  if (n_big == 0) return MGX_OK;
+  mgx_scope bufs(ctx);
+  uint64_t *caps = nullptr, *pool_off = nullptr;
+  MGX_TRY(bufs.alloc(&caps, n_big));
+  hipLaunchKernelGGL(k_big_caps, dim3((uint32_t)grid_for(n_big)), dim3(kBlock), 0,
+                     ctx->stream, n_big, A->big_rows, A->row_ptr, caps);
+  MGX_TRY(own.alloc(&pool_off, n_big + 1));
+  MGX_TRY(mgx_with_temp(ctx, "louvain pool scan", [&](void *tmp, size_t &bytes) {
+    return rocprim::exclusive_scan(tmp, bytes, caps, pool_off, (uint64_t)0, n_big,
+                                   rocprim::plus<uint64_t>(), ctx->stream);
+  }));
+  uint64_t last_off = 0, last_cap = 0;
+  MGX_HIP_TRY(hipMemcpyAsync(&last_off, pool_off + n_big - 1, 8, hipMemcpyDeviceToHost,
+                             ctx->stream));
+  MGX_TRY(read_back(ctx, caps + n_big - 1, &last_cap));
+  A->pool_total = last_off + last_cap;
+  MGX_HIP_TRY(hipMemcpyAsync(pool_off + n_big, &A->pool_total, 8, hipMemcpyHostToDevice,
+                             ctx->stream));
+  A->pool_off = pool_off;
+  MGX_TRY(own.alloc(&A->pool_keys, (int64_t)A->pool_total));
+  MGX_TRY(own.alloc(&A->pool_vals, (int64_t)A->pool_total));
+  return MGX_OK;
+}
+
+// The sweep loop. assign = {past, curr, target}, rotated after every adopted
+// sweep (parallelLouvainMethod.cpp:268-274); on return assign[0] is the
+// adopted assignment and *out_mod its modularity.
+mgx_status run_sweeps(mgx_context *ctx, SweepArgs A, double lower, double thresh,
+                      int32_t *(&assign)[3], double *out_mod, int64_t *iters_out) {
+  const int64_t nv = A.nv;
+  double prev_mod = -1.0;
   int64_t iters = 0;
-  int32_t *p_past = past.as<int32_t>(), *p_curr = curr.as<int32_t>(),
-          *p_target = target.as<int32_t>();
   while (true) {
     ++iters;
-    MGX_HIP_TRY(hipMemsetAsync(scalars.p, 0, 16, ctx->stream));  // e_xx, a2_x
-    A.curr = p_curr;
-    A.target = p_target;
-    MGX_LDBG(ctx, "iter=%lld pre-sweep", (long long)iters);
-    MGX_LTRACE("it=%lld k_sweep_empty", (long long)iters);
+    MGX_HIP_TRY(hipMemsetAsync(A.e_xx, 0, 16, ctx->stream));  // e_xx, a2_x
+    A.curr = assign[1];
+    A.target = assign[2];
     hipLaunchKernelGGL(k_sweep_empty, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0,
-                       ctx->stream, nv, L.row_ptr, p_target);
-    MGX_LDBG(ctx, "iter=%lld after-empty", (long long)iters);
-    if (n_small > 0) {
-      const int64_t waves_needed = n_small;
-      const int64_t blocks = grid_for(waves_needed * 64, 4096);
-      MGX_LTRACE("it=%lld k_sweep_small", (long long)iters);
-      static const int skip_small = louvain_diag("MGX_LOUVAIN_SKIP_SMALL");
-      if (!skip_small)
-        hipLaunchKernelGGL(k_sweep_small, dim3((uint32_t)blocks), dim3(kBlock), 0,
-                           ctx->stream, A);
-      static const int sync_after = louvain_diag("MGX_LOUVAIN_SYNC_AFTER");
-      if (sync_after) {
-        hipError_t se = hipStreamSynchronize(ctx->stream);
-        hipError_t le = hipGetLastError();
-        if (se != hipSuccess || le != hipSuccess)
-          MGX_LTRACE("it=%lld SMALL sync=%s last=%s", (long long)iters,
-                     hipGetErrorString(se), hipGetErrorString(le));
-      }
-      MGX_LTRACE("it=%lld k_sweep_small launched", (long long)iters);
+                       ctx->stream, nv, A.row_ptr, A.target);
+    if (A.n_small > 0)
+      hipLaunchKernelGGL(k_sweep_small, dim3((uint32_t)grid_for(A.n_small * 64, 4096)),
+                         dim3(kBlock), 0, ctx->stream, A);
+    if (A.n_big > 0) {
+      hipLaunchKernelGGL(mgx_k_fill<int32_t>,
+                         dim3((uint32_t)grid_for((int64_t)A.pool_total)), dim3(kBlock), 0,
+                         ctx->stream, (int64_t)A.pool_total, -1, A.pool_keys);
+      MGX_HIP_TRY(hipMemsetAsync(A.pool_vals, 0, A.pool_total * 8, ctx->stream));
+      hipLaunchKernelGGL(k_sweep_big, dim3((uint32_t)(A.n_big < 4096 ? A.n_big : 4096)),
+                         dim3(kBlock), 0, ctx->stream, A);
     }
-    MGX_LDBG(ctx, "iter=%lld after-small", (long long)iters);
-    if (n_big > 0) {
-      if (!A.inkernel_clear) {
-        MGX_LTRACE("it=%lld pool_clear", (long long)iters);
-        hipLaunchKernelGGL(mgx_k_fill<int32_t>,
-                           dim3((uint32_t)grid_for((int64_t)pool_total)), dim3(kBlock), 0,
-                           ctx->stream, (int64_t)pool_total, -1, pool_keys.as<int32_t>());
-        MGX_HIP_TRY(hipMemsetAsync(pool_vals.p, 0, pool_total * 8, ctx->stream));
-      }
-      const int64_t blocks = n_big < 4096 ? n_big : 4096;
-      MGX_LTRACE("it=%lld k_sweep_big", (long long)iters);
-      static const int skip_big = louvain_diag("MGX_LOUVAIN_SKIP_BIG");
-      if (!skip_big)
-        hipLaunchKernelGGL(k_sweep_big, dim3((uint32_t)blocks), dim3(kBlock), 0,
-                           ctx->stream, A);
-      static const int sync_after_b = louvain_diag("MGX_LOUVAIN_SYNC_AFTER");
-      if (sync_after_b) {
-        hipError_t se = hipStreamSynchronize(ctx->stream);
-        hipError_t le = hipGetLastError();
-        if (se != hipSuccess || le != hipSuccess)
-          MGX_LTRACE("it=%lld BIG sync=%s last=%s", (long long)iters,
-                     hipGetErrorString(se), hipGetErrorString(le));
-      }
-      MGX_LTRACE("it=%lld k_sweep_big launched", (long long)iters);
-    }
-    MGX_LDBG(ctx, "iter=%lld after-big", (long long)iters);
-    MGX_LDBG(ctx, "iter=%lld post-sweep", (long long)iters);
-    MGX_LTRACE("it=%lld k_sum_sq", (long long)iters);
     hipLaunchKernelGGL(k_sum_sq_f64, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0,
-                       ctx->stream, nv, cinfo_deg.as<double>(), scalars.as<double>() + 1);
+                       ctx->stream, nv, A.cinfo_deg, A.e_xx + 1);
     double exx_a2x[2] = {0.0, 0.0};
-    MGX_HIP_TRY(hipMemcpyAsync(exx_a2x, scalars.p, 16, hipMemcpyDeviceToHost, ctx->stream));
-    MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (louvain_trace()) {
-      uint32_t ge[4] = {0, 0, 0, 0};
-      MGX_HIP_TRY(hipMemcpyAsync(ge, A.guard, 16, hipMemcpyDeviceToHost, ctx->stream));
-      MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-      if (ge[0] || ge[1])
-        MGX_LTRACE("it=%lld GUARD bits=%u oob=%u row=%u cid=%u", (long long)iters, ge[0],
-                   ge[1], ge[2], ge[3]);
-    }
-    curr_mod = exx_a2x[0] * constant - exx_a2x[1] * constant * constant;
-    if (louvain_debug() && (iters < 10 || iters % 500 == 0)) {
-      fprintf(stderr, "[louvain] iter=%lld exx=%.12g a2x=%.12g mod=%.12g prev=%.12g\n",
-              (long long)iters, exx_a2x[0], exx_a2x[1], curr_mod, prev_mod);
-      fflush(stderr);
-    }
+    MGX_TRY(read_back(ctx, A.e_xx, exx_a2x, 2));
+    const double curr_mod =
+        exx_a2x[0] * A.constant - exx_a2x[1] * A.constant * A.constant;
     if ((curr_mod - prev_mod) < thresh) break;
     prev_mod = curr_mod;
     if (prev_mod < lower) prev_mod = lower;
-    MGX_LTRACE("it=%lld k_apply_updates", (long long)iters);
     hipLaunchKernelGGL(k_apply_updates, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0,
-                       ctx->stream, nv, cinfo_deg.as<double>(), cinfo_size.as<int32_t>(),
-                       cupd_deg.as<double>(), cupd_size.as<int32_t>());
-    // rotation (parallelLouvainMethod.cpp:268-274)
-    int32_t *tmp = p_past;
-    p_past = p_curr;
-    p_curr = p_target;
-    p_target = tmp;
+                       ctx->stream, nv, A.cinfo_deg, A.cinfo_size, A.cupd_deg, A.cupd_size);
+    int32_t *past = assign[0];
+    assign[0] = assign[1];
+    assign[1] = assign[2];
+    assign[2] = past;
     if (iters > 100000) break;  // matches runMultiPhaseBasic's totItr cap scale
   }
-
-  {
-    uint32_t ge[4] = {0, 0, 0, 0};
-    MGX_HIP_TRY(hipMemcpyAsync(ge, A.guard, 16, hipMemcpyDeviceToHost, ctx->stream));
-    MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ge[0] || ge[1]) {
-      fprintf(stderr,
-              "[louvain] GUARD FIRED region_bits=%u oob_count=%u first_row=%u "
-              "first_cid=%u (nv=%lld iters=%lld) — clamped to stay-put; "
-              "please report\n",
-              ge[0], ge[1], ge[2], ge[3], (long long)nv, (long long)iters);
-      fflush(stderr);
-      const char *strict = getenv("MGX_LOUVAIN_STRICT");
-      if (strict && atoi(strict)) {
-        mgx_set_error("louvain device guard fired (region_bits=%u oob=%u row=%u cid=%u)",
-                      ge[0], ge[1], ge[2], ge[3]);
-        return MGX_ERR_HIP;
-      }
-    } else if (louvain_debug()) {
-      fprintf(stderr, "[louvain] guard clean (nv=%lld)\n", (long long)nv);
-      fflush(stderr);
-    }
-  }
-  MGX_HIP_TRY(hipMemcpyAsync(C, p_past, nv * 4, hipMemcpyDeviceToDevice, ctx->stream));
-  MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
   // The reference's sweep loop returns prevMod — the (Lower-clamped)
   // modularity of the ADOPTED assignment, not the last computed currMod
   // (parallelLouvainMethod.cpp:307). The two differ by < thresh, which
   // flips the phase-continue decision at loose thresholds.
   *out_mod = prev_mod;
   *iters_out = iters;
+  return MGX_OK;
+}
+
+// Guard read-back after a level's sweeps.
+mgx_status check_sweep_guard(mgx_context *ctx, const SweepArgs &A, int64_t iters) {
+  uint32_t ge[4] = {0, 0, 0, 0};
+  MGX_TRY(read_back(ctx, A.guard, ge, 4));
+  if (!ge[0] && !ge[1]) return MGX_OK;
+  fprintf(stderr,
+          "[louvain] GUARD FIRED region_bits=%u oob_count=%u first_row=%u "
+          "first_cid=%u (nv=%lld iters=%lld) — clamped to stay-put; "
+          "please report\n",
+          ge[0], ge[1], ge[2], ge[3], (long long)A.nv, (long long)iters);
+  fflush(stderr);
+  if (louvain_strict()) {
+    mgx_set_error("louvain device guard fired (region_bits=%u oob=%u row=%u cid=%u)", ge[0],
+                  ge[1], ge[2], ge[3]);
+    return MGX_ERR_HIP;
+  }
+  return MGX_OK;
+}
+
+// Runs parallelLouvianMethod on one level. C (device i32[nv]) receives
+// pastCommAss. Returns modularity via *out_mod.
+mgx_status louvain_level(mgx_context *ctx, const Level &L, const RowLists &R, double lower,
+                         double thresh, int32_t *C, double *out_mod, int64_t *iters_out) {
+  const int64_t nv = L.nv;
+  mgx_scope bufs(ctx);
+  SweepArgs A{};
+  MGX_TRY(init_level_state(bufs, L, R, &A));
+  MGX_TRY(size_hub_pool(bufs, &A));
+  int32_t *assign[3] = {nullptr, nullptr, nullptr};
+  for (int32_t *&a : assign) MGX_TRY(bufs.alloc(&a, nv));
+  hipLaunchKernelGGL(mgx_k_iota<int32_t>, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0,
+                     ctx->stream, nv, assign[0]);
+  hipLaunchKernelGGL(mgx_k_iota<int32_t>, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0,
+                     ctx->stream, nv, assign[1]);
+  MGX_TRY(run_sweeps(ctx, A, lower, thresh, assign, out_mod, iters_out));
+  MGX_TRY(check_sweep_guard(ctx, A, *iters_out));
+  MGX_HIP_TRY(hipMemcpyAsync(C, assign[0], nv * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
   MGX_HIP_TRY(hipGetLastError());
   return MGX_OK;
 }
 
 // renumberClustersContiguously: new id = rank of community's min vertex.
 mgx_status renumber(mgx_context *ctx, int32_t *C, int64_t nv, int64_t *n_clusters) {
-  DevBuf rep, keys_out, cand, cand_out, newid, nact;
-  MGX_HIP_TRY(rep.alloc(ctx, nv * 4));
+  mgx_scope bufs(ctx);
+  int32_t *rep = nullptr, *rep_sorted = nullptr, *cand = nullptr, *cand_sorted = nullptr,
+          *newid = nullptr;
+  unsigned long long *count = nullptr;
+  MGX_TRY(bufs.alloc(&rep, nv));
   hipLaunchKernelGGL(mgx_k_fill<int32_t>, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0,
-                     ctx->stream, nv, INT32_MAX, rep.as<int32_t>());
+                     ctx->stream, nv, INT32_MAX, rep);
   hipLaunchKernelGGL(k_rep_min, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0, ctx->stream,
-                     nv, C, rep.as<int32_t>());
+                     nv, C, rep);
   // sort (rep, c) ascending by rep; INT32_MAX reps (inactive ids) sort last.
-  MGX_HIP_TRY(cand.alloc(ctx, nv * 4));
-  MGX_HIP_TRY(cand_out.alloc(ctx, nv * 4));
-  MGX_HIP_TRY(keys_out.alloc(ctx, nv * 4));
+  MGX_TRY(bufs.alloc(&cand, nv));
+  MGX_TRY(bufs.alloc(&cand_sorted, nv));
+  MGX_TRY(bufs.alloc(&rep_sorted, nv));
   hipLaunchKernelGGL(mgx_k_iota<int32_t>, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0,
-                     ctx->stream, nv, cand.as<int32_t>());
+                     ctx->stream, nv, cand);
   MGX_TRY(mgx_with_temp(ctx, "louvain renumber sort", [&](void *tmp, size_t &bytes) {
-    return rocprim::radix_sort_pairs(tmp, bytes, (uint32_t *)rep.p, (uint32_t *)keys_out.p,
-                                     cand.as<int32_t>(), cand_out.as<int32_t>(), nv, 0, 32,
-                                     ctx->stream);
+    return rocprim::radix_sort_pairs(tmp, bytes, (uint32_t *)rep, (uint32_t *)rep_sorted,
+                                     cand, cand_sorted, nv, 0, 32, ctx->stream);
   }));
-  // count active = reps != INT32_MAX: binary property; count via reduce on
-  // host copy of the boundary — simpler: count nonzero with a kernel.
-  DevBuf count;
-  MGX_HIP_TRY(count.alloc(ctx, 8));
-  MGX_HIP_TRY(hipMemsetAsync(count.p, 0, 8, ctx->stream));
-  {
-    struct K {
-      static __global__ void count_active(int64_t n, const uint32_t *sorted_rep,
-                                          unsigned long long *out) {
-        unsigned long long acc = 0;
-        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-             i += (int64_t)gridDim.x * blockDim.x)
-          if (sorted_rep[i] != 0x7FFFFFFFu) ++acc;
-        __shared__ unsigned long long red[kBlock / 64];
-        for (int o = 32; o; o >>= 1) acc += __shfl_down(acc, o, 64);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-          unsigned long long s = 0;
-          for (int i = 0; i < kBlock / 64; ++i) s += red[i];
-          atomicAdd(out, s);
-        }
-      }
-    };
-    hipLaunchKernelGGL(K::count_active, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0,
-                       ctx->stream, nv, (uint32_t *)keys_out.p,
-                       (unsigned long long *)count.p);
-  }
+  MGX_TRY(bufs.alloc(&count, 1));
+  MGX_HIP_TRY(hipMemsetAsync(count, 0, 8, ctx->stream));
+  hipLaunchKernelGGL(k_count_active, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0,
+                     ctx->stream, nv, (const uint32_t *)rep_sorted, count);
   unsigned long long n_active = 0;
-  MGX_HIP_TRY(hipMemcpyAsync(&n_active, count.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-  MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  MGX_LTRACE("renumber nv=%lld n_active=%llu", (long long)nv,
-             (unsigned long long)n_active);
-  MGX_HIP_TRY(newid.alloc(ctx, nv * 4));
+  MGX_TRY(read_back(ctx, count, &n_active));
+  MGX_TRY(bufs.alloc(&newid, nv));
   hipLaunchKernelGGL(k_newid_from_sorted, dim3((uint32_t)grid_for((int64_t)n_active)),
-                     dim3(kBlock), 0, ctx->stream, (int64_t)n_active,
-                     cand_out.as<int32_t>(), newid.as<int32_t>());
+                     dim3(kBlock), 0, ctx->stream, (int64_t)n_active, cand_sorted, newid);
   hipLaunchKernelGGL(k_remap, dim3((uint32_t)grid_for(nv)), dim3(kBlock), 0, ctx->stream,
-                     nv, C, newid.as<int32_t>());
+                     nv, C, newid);
   MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
   *n_clusters = (int64_t)n_active;
   return MGX_OK;
 }
 
-// buildNextLevelGraphOpt: aggregate (C[i] >= C[tail]) pairs, always-present
-// self loops, mirrored lower pairs.
-mgx_status coarsen(mgx_context *ctx, const Level &in, const int32_t *C, int64_t n_clusters,
-                   Level *out) {
+// coarsen's transient buffers, and what each of its steps hands to the next.
+struct CoarsenBufs {
+  int32_t *row_of_entry = nullptr;                                      // [ne2]
+  uint64_t *keys = nullptr, *keys_sorted = nullptr, *u_keys = nullptr;  // [ne2]
+  double *vals = nullptr, *vals_sorted = nullptr, *u_vals = nullptr;    // [ne2]
+  int64_t n_pairs = 0;  // unique (ci >= ct) pairs at the front of u_keys / u_vals
+  uint32_t *counts = nullptr, *self_present = nullptr;  // [ncl]
+  unsigned long long oob = 0;  // pairs k_pair_counts dropped as out of range
+  uint32_t total = 0;          // entries of the coarse CSR
+};
+
+// Pair keys + sort + reduce: one (ci, ct, summed weight) per community pair
+// with ci >= ct.
+mgx_status reduce_pairs(mgx_scope &own, const Level &in, const RowLists &R, const int32_t *C,
+                        CoarsenBufs *B) {
+  mgx_context *ctx = own.ctx;
   const int64_t ne2 = in.ne2;
-  DevBuf row_of_entry, keys, vals, keys_sorted, vals_sorted, u_keys, u_vals, u_count;
-  MGX_HIP_TRY(row_of_entry.alloc(ctx, ne2 * 4));
-  {
-    // Binned expansion of the CSR's row ids (hub rows block-parallel).
-    DevBuf counters, srows, brows;
-    MGX_HIP_TRY(counters.alloc(ctx, 4 * 4));
-    MGX_HIP_TRY(hipMemsetAsync(counters.p, 0, 16, ctx->stream));
-    hipLaunchKernelGGL(k_classify_rows, dim3((uint32_t)grid_for(in.nv)), dim3(kBlock), 0,
-                       ctx->stream, in.nv, in.row_ptr, counters.as<uint32_t>(),
-                       counters.as<uint32_t>() + 1);
-    uint32_t hc[2] = {0, 0};
-    MGX_HIP_TRY(hipMemcpyAsync(hc, counters.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-    MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    MGX_HIP_TRY(srows.alloc(ctx, (hc[0] > 0 ? hc[0] : 1) * 4));
-    MGX_HIP_TRY(brows.alloc(ctx, (hc[1] > 0 ? hc[1] : 1) * 4));
-    MGX_HIP_TRY(hipMemsetAsync(counters.p, 0, 16, ctx->stream));
-    hipLaunchKernelGGL(k_fill_rows, dim3((uint32_t)grid_for(in.nv)), dim3(kBlock), 0,
-                       ctx->stream, in.nv, in.row_ptr, srows.as<int32_t>(),
-                       brows.as<int32_t>(), counters.as<uint32_t>(),
-                       counters.as<uint32_t>() + 1);
-    if (hc[0] > 0)
-      hipLaunchKernelGGL(k_row_of_entry_small, dim3((uint32_t)grid_for(hc[0])),
-                         dim3(kBlock), 0, ctx->stream, (int64_t)hc[0], srows.as<int32_t>(),
-                         in.row_ptr, row_of_entry.as<int32_t>());
-    if (hc[1] > 0)
-      hipLaunchKernelGGL(k_row_of_entry_big,
-                         dim3((uint32_t)(hc[1] < 4096 ? hc[1] : 4096)), dim3(kBlock), 0,
-                         ctx->stream, (int64_t)hc[1], brows.as<int32_t>(), in.row_ptr,
-                         row_of_entry.as<int32_t>());
-    MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  }
-  MGX_HIP_TRY(keys.alloc(ctx, ne2 * 8));
-  MGX_HIP_TRY(vals.alloc(ctx, ne2 * 8));
+  // Binned expansion of the CSR's row ids (hub rows block-parallel).
+  MGX_TRY(own.alloc(&B->row_of_entry, ne2));
+  if (R.n_small > 0)
+    hipLaunchKernelGGL(k_row_of_entry_small, dim3((uint32_t)grid_for(R.n_small)),
+                       dim3(kBlock), 0, ctx->stream, R.n_small, R.small, in.row_ptr,
+                       B->row_of_entry);
+  if (R.n_big > 0)
+    hipLaunchKernelGGL(k_row_of_entry_big, dim3((uint32_t)(R.n_big < 4096 ? R.n_big : 4096)),
+                       dim3(kBlock), 0, ctx->stream, R.n_big, R.big, in.row_ptr,
+                       B->row_of_entry);
+  MGX_TRY(own.alloc(&B->keys, ne2));
+  MGX_TRY(own.alloc(&B->vals, ne2));
   const uint64_t sentinel = ~0ull;
   hipLaunchKernelGGL(k_pair_keys, dim3((uint32_t)grid_for(ne2)), dim3(kBlock), 0,
-                     ctx->stream, ne2, in.col, in.row_ptr, in.nv, C, in.w,
-                     row_of_entry.as<int32_t>(), keys.as<uint64_t>(), vals.as<double>(),
-                     sentinel);
-  MGX_HIP_TRY(keys_sorted.alloc(ctx, ne2 * 8));
-  MGX_HIP_TRY(vals_sorted.alloc(ctx, ne2 * 8));
-  DevBuf d_bad;
-  MGX_HIP_TRY(d_bad.alloc(ctx, 8));
-  MGX_HIP_TRY(hipMemsetAsync(d_bad.p, 0, 8, ctx->stream));
-  if (louvain_trace()) {
-    hipLaunchKernelGGL(k_validate_keys, dim3((uint32_t)grid_for(ne2)), dim3(kBlock), 0,
-                       ctx->stream, ne2, keys.as<uint64_t>(), n_clusters, sentinel,
-                       (unsigned long long *)d_bad.p);
-    unsigned long long bad = 0;
-    MGX_HIP_TRY(hipMemcpyAsync(&bad, d_bad.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-    MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    MGX_LTRACE("coarsen PAIRKEYS bad=%llu", bad);
-    MGX_HIP_TRY(hipMemsetAsync(d_bad.p, 0, 8, ctx->stream));
-  }
+                     ctx->stream, ne2, in.col, in.row_ptr, in.nv, C, in.w, B->row_of_entry,
+                     B->keys, B->vals, sentinel);
+  MGX_TRY(own.alloc(&B->keys_sorted, ne2));
+  MGX_TRY(own.alloc(&B->vals_sorted, ne2));
   MGX_TRY(mgx_with_temp(ctx, "louvain coarsen pair sort", [&](void *tmp, size_t &bytes) {
-    return rocprim::radix_sort_pairs(tmp, bytes, keys.as<uint64_t>(),
-                                     keys_sorted.as<uint64_t>(), vals.as<double>(),
-                                     vals_sorted.as<double>(), ne2, 0, 64, ctx->stream);
+    return rocprim::radix_sort_pairs(tmp, bytes, B->keys, B->keys_sorted, B->vals,
+                                     B->vals_sorted, ne2, 0, 64, ctx->stream);
   }));
-  MGX_HIP_TRY(u_keys.alloc(ctx, ne2 * 8));
-  MGX_HIP_TRY(u_vals.alloc(ctx, ne2 * 8));
-  MGX_HIP_TRY(u_count.alloc(ctx, 8));
+  unsigned int *u_count = nullptr;
+  MGX_TRY(own.alloc(&B->u_keys, ne2));
+  MGX_TRY(own.alloc(&B->u_vals, ne2));
+  MGX_TRY(own.alloc(&u_count, 1));
   MGX_TRY(mgx_with_temp(ctx, "louvain coarsen reduce_by_key", [&](void *tmp, size_t &bytes) {
-    return rocprim::reduce_by_key(tmp, bytes, keys_sorted.as<uint64_t>(),
-                                  vals_sorted.as<double>(), ne2, u_keys.as<uint64_t>(),
-                                  u_vals.as<double>(), (unsigned int *)u_count.p,
-                                  rocprim::plus<double>(), rocprim::equal_to<uint64_t>(),
-                                  ctx->stream);
+    return rocprim::reduce_by_key(tmp, bytes, B->keys_sorted, B->vals_sorted, ne2, B->u_keys,
+                                  B->u_vals, u_count, rocprim::plus<double>(),
+                                  rocprim::equal_to<uint64_t>(), ctx->stream);
   }));
   unsigned int n_unique = 0;
-  MGX_HIP_TRY(hipMemcpyAsync(&n_unique, u_count.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-  MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  MGX_LTRACE("coarsen ne2=%lld n_unique=%u", (long long)ne2, n_unique);
-  if (louvain_trace() && n_unique > 0) {
-    hipLaunchKernelGGL(k_validate_keys, dim3((uint32_t)grid_for((int64_t)n_unique)),
-                       dim3(kBlock), 0, ctx->stream, (int64_t)n_unique,
-                       u_keys.as<uint64_t>(), n_clusters, sentinel,
-                       (unsigned long long *)d_bad.p);
-    unsigned long long bad = 0;
-    MGX_HIP_TRY(hipMemcpyAsync(&bad, d_bad.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-    MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    MGX_LTRACE("coarsen UKEYS bad=%llu", bad);
-    MGX_HIP_TRY(hipMemsetAsync(d_bad.p, 0, 8, ctx->stream));
-  }
+  MGX_TRY(read_back(ctx, u_count, &n_unique));
   // drop the sentinel group if present (it sorts last)
-  int64_t n_pairs = n_unique;
-  if (n_pairs > 0) {
+  B->n_pairs = n_unique;
+  if (B->n_pairs > 0) {
     uint64_t last_key = 0;
-    MGX_HIP_TRY(hipMemcpyAsync(&last_key, u_keys.as<uint64_t>() + n_pairs - 1, 8,
-                               hipMemcpyDeviceToHost, ctx->stream));
-    MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (last_key == sentinel) --n_pairs;
+    MGX_TRY(read_back(ctx, B->u_keys + B->n_pairs - 1, &last_key));
+    if (last_key == sentinel) --B->n_pairs;
   }
+  return MGX_OK;
+}
 
-  if (louvain_trace() && n_pairs > 0) {
-    // probe: first/last unique keys + a counts sample after the passes
-    uint64_t k0 = 0, k1 = 0;
-    (void)hipMemcpyAsync(&k0, u_keys.as<uint64_t>(), 8, hipMemcpyDeviceToHost,
-                         ctx->stream);
-    (void)hipMemcpyAsync(&k1, u_keys.as<uint64_t>() + n_pairs - 1, 8,
-                         hipMemcpyDeviceToHost, ctx->stream);
-    (void)hipStreamSynchronize(ctx->stream);
-    MGX_LTRACE("coarsen ukeys[0]=(%d,%d) ukeys[last]=(%d,%d)", (int)(k0 >> 32),
-               (int)(uint32_t)k0, (int)(k1 >> 32), (int)(uint32_t)k1);
-  }
-  // CSR counts + self presence.
-  DevBuf counts, self_present;
-  MGX_HIP_TRY(counts.alloc(ctx, n_clusters * 4));
-  MGX_HIP_TRY(self_present.alloc(ctx, n_clusters * 4));
-  MGX_HIP_TRY(hipMemsetAsync(counts.p, 0, n_clusters * 4, ctx->stream));
-  MGX_HIP_TRY(hipMemsetAsync(self_present.p, 0, n_clusters * 4, ctx->stream));
-  if (n_pairs > 0)
-    hipLaunchKernelGGL(k_pair_counts, dim3((uint32_t)grid_for(n_pairs)), dim3(kBlock), 0,
-                       ctx->stream, n_pairs, u_keys.as<uint64_t>(), n_clusters,
-                       counts.as<uint32_t>(), self_present.as<uint32_t>(),
-                       (unsigned long long *)d_bad.p);
-  {
-    unsigned long long oob = 0;
-    MGX_HIP_TRY(hipMemcpyAsync(&oob, d_bad.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-    MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (oob) {
-      fprintf(stderr,
-              "[louvain] COARSEN GUARD: %llu out-of-range pair ids dropped "
-              "(ncl=%lld) — please report\n",
-              oob, (long long)n_clusters);
-      fflush(stderr);
-      const char *strict = getenv("MGX_LOUVAIN_STRICT");
-      if (strict && atoi(strict)) {
-        mgx_set_error("louvain coarsen guard fired (%llu bad pair ids)", oob);
-        return MGX_ERR_HIP;
-      }
-    }
-  }
+// Counts -> row_ptr: the coarse CSR's row_ptr (in `levels`) from the pair
+// histogram plus one self loop per cluster; leaves B->oob and B->total.
+mgx_status build_row_ptr(mgx_scope &own, mgx_scope &levels, int64_t n_clusters,
+                         CoarsenBufs *B, Level *out) {
+  mgx_context *ctx = own.ctx;
+  unsigned long long *d_oob = nullptr;
+  MGX_TRY(own.alloc(&B->counts, n_clusters));
+  MGX_TRY(own.alloc(&B->self_present, n_clusters));
+  MGX_TRY(own.alloc(&d_oob, 1));
+  MGX_HIP_TRY(hipMemsetAsync(B->counts, 0, n_clusters * 4, ctx->stream));
+  MGX_HIP_TRY(hipMemsetAsync(B->self_present, 0, n_clusters * 4, ctx->stream));
+  MGX_HIP_TRY(hipMemsetAsync(d_oob, 0, 8, ctx->stream));
+  if (B->n_pairs > 0)
+    hipLaunchKernelGGL(k_pair_counts, dim3((uint32_t)grid_for(B->n_pairs)), dim3(kBlock), 0,
+                       ctx->stream, B->n_pairs, B->u_keys, n_clusters, B->counts,
+                       B->self_present, d_oob);
   hipLaunchKernelGGL(k_add_missing_self, dim3((uint32_t)grid_for(n_clusters)), dim3(kBlock),
-                     0, ctx->stream, n_clusters, self_present.as<uint32_t>(),
-                     counts.as<uint32_t>());
-  if (louvain_trace()) {
-    uint32_t c0[4] = {0, 0, 0, 0};
-    (void)hipMemcpyAsync(c0, counts.p, 16, hipMemcpyDeviceToHost, ctx->stream);
-    hipError_t se = hipStreamSynchronize(ctx->stream);
-    MGX_LTRACE("coarsen counts[0..3]=%u,%u,%u,%u sync=%s", c0[0], c0[1], c0[2], c0[3],
-               hipGetErrorString(se));
-  }
-
-  out->nv = n_clusters;
+                     0, ctx->stream, n_clusters, B->self_present, B->counts);
   ctx->ensure_margin((size_t)(n_clusters + 1) * 4);
-  MGX_HIP_TRY(mgx_hip_malloc(&out->row_ptr, (n_clusters + 1) * 4));
-  if (louvain_trace()) {
-    // Pre-scan probe: counts must still hold the pair histogram, and the
-    // freshly hipMalloc'd row_ptr must not alias the pool-allocated counts
-    // (the r02 corruption signature is an in-place exclusive scan -> zeros).
-    uint32_t c1[4] = {0, 0, 0, 0};
-    (void)hipMemcpyAsync(c1, counts.p, 16, hipMemcpyDeviceToHost, ctx->stream);
-    (void)hipStreamSynchronize(ctx->stream);
-    MGX_LTRACE("coarsen prescan counts[0..3]=%u,%u,%u,%u", c1[0], c1[1], c1[2], c1[3]);
-    const char *rp0 = (const char *)out->row_ptr;
-    const char *rp1 = rp0 + (size_t)(n_clusters + 1) * 4;
-    const char *cn0 = (const char *)counts.p, *cn1 = cn0 + (size_t)n_clusters * 4;
-    const char *ws0 = (const char *)ctx->workspace;
-    const char *ws1 = ws0 + ctx->workspace_bytes;
-    MGX_LTRACE("coarsen prescan row_ptr=[%p,%p) counts=[%p,%p) ws=[%p,%p)", rp0, rp1, cn0,
-               cn1, ws0, ws1);
-    if (rp0 < cn1 && cn0 < rp1) MGX_LTRACE("coarsen ALIAS row_ptr overlaps counts");
-    if (rp0 < ws1 && ws0 < rp1) MGX_LTRACE("coarsen ALIAS row_ptr overlaps workspace");
-    if (cn0 < ws1 && ws0 < cn1) MGX_LTRACE("coarsen ALIAS counts overlaps workspace");
-  }
-  // exclusive scan counts -> row_ptr
+  MGX_TRY(levels.alloc_plain(&out->row_ptr, n_clusters + 1));
   MGX_TRY(mgx_with_temp(ctx, "louvain coarsen row_ptr scan", [&](void *tmp, size_t &bytes) {
-    return rocprim::exclusive_scan(tmp, bytes, counts.as<uint32_t>(), out->row_ptr, 0u,
-                                   n_clusters, rocprim::plus<uint32_t>(), ctx->stream);
+    return rocprim::exclusive_scan(tmp, bytes, B->counts, out->row_ptr, 0u, n_clusters,
+                                   rocprim::plus<uint32_t>(), ctx->stream);
   }));
   uint32_t last_off = 0, last_cnt = 0;
   MGX_HIP_TRY(hipMemcpyAsync(&last_off, out->row_ptr + n_clusters - 1, 4,
                              hipMemcpyDeviceToHost, ctx->stream));
-  MGX_HIP_TRY(hipMemcpyAsync(&last_cnt, counts.as<uint32_t>() + n_clusters - 1, 4,
-                             hipMemcpyDeviceToHost, ctx->stream));
-  MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  if (louvain_trace()) {
-    uint32_t rp[4] = {0, 0, 0, 0}, cs[4] = {0, 0, 0, 0};
-    (void)hipMemcpyAsync(rp, out->row_ptr, 16, hipMemcpyDeviceToHost, ctx->stream);
-    (void)hipMemcpyAsync(cs, counts.p, 16, hipMemcpyDeviceToHost, ctx->stream);
-    (void)hipStreamSynchronize(ctx->stream);
-    MGX_LTRACE("coarsen scan rp[0..3]=%u,%u,%u,%u cs[0..3]=%u,%u,%u,%u last_off=%u "
-               "last_cnt=%u",
-               rp[0], rp[1], rp[2], rp[3], cs[0], cs[1], cs[2], cs[3], last_off,
-               last_cnt);
-  }
-  const uint32_t total = last_off + last_cnt;
-  MGX_HIP_TRY(hipMemcpyAsync(out->row_ptr + n_clusters, &total, 4, hipMemcpyHostToDevice,
+  MGX_HIP_TRY(hipMemcpyAsync(&last_cnt, B->counts + n_clusters - 1, 4, hipMemcpyDeviceToHost,
                              ctx->stream));
-  out->ne2 = total;
-  MGX_LTRACE("coarsen n_pairs=%lld ncl=%lld total=%u", (long long)n_pairs,
-             (long long)n_clusters, total);
+  MGX_TRY(read_back(ctx, d_oob, &B->oob));
+  B->total = last_off + last_cnt;
+  MGX_HIP_TRY(hipMemcpyAsync(out->row_ptr + n_clusters, &B->total, 4, hipMemcpyHostToDevice,
+                             ctx->stream));
+  return MGX_OK;
+}
+
+// The gates between the counting and the scatters: each turns what would be an
+// out-of-bounds scatter into a clean error.
+mgx_status coarsen_gates(mgx_context *ctx, const Level &in, const CoarsenBufs &B,
+                         const Level &out) {
+  const int64_t n_clusters = out.nv, ne2 = in.ne2;
+  if (B.oob) {
+    fprintf(stderr,
+            "[louvain] COARSEN GUARD: %llu out-of-range pair ids dropped "
+            "(ncl=%lld) — please report\n",
+            B.oob, (long long)n_clusters);
+    fflush(stderr);
+    if (louvain_strict()) {
+      mgx_set_error("louvain coarsen guard fired (%llu bad pair ids)", B.oob);
+      return MGX_ERR_HIP;
+    }
+  }
   // Consistency gate: total = 2*offdiag + ncl >= max(n_pairs - dropped, ncl).
   // A smaller total means the counts/row_ptr memory was trampled between the
   // passes (the r02 storm signature: plain-hipMalloc row_ptr aliasing the
   // pool-allocated counts block turned the exclusive scan in-place -> all
   // zeros); scattering against it would write OOB, so fail cleanly instead.
-  if ((int64_t)total < n_clusters) {
+  if ((int64_t)B.total < n_clusters) {
     mgx_set_error(
         "louvain coarsen inconsistent (total=%u < ncl=%lld, n_pairs=%lld) — "
         "device memory corruption detected",
-        total, (long long)n_clusters, (long long)n_pairs);
+        B.total, (long long)n_clusters, (long long)B.n_pairs);
     return MGX_ERR_HIP;
   }
+  // ALWAYS-ON overlap gate. The box's ROCm 7.0.x runtime mis-places
+  // multi-GiB hipMallocs once the VA space is fragmented: at RMAT-25+
+  // the total-sized col/w come back overlapping five live buffers (the
+  // fit check appears to use only the low 32 bits of the size; an
+  // isolated fresh-process repro allocates the same sizes correctly).
+  // Scattering through such a mapping faults the GPU, so detect the
+  // overlap host-side and fail cleanly instead.
+  const size_t entries = B.total > 0 ? B.total : 1;
+  struct Rg {
+    const void *p;
+    size_t bytes;
+  } rgs[] = {
+      {B.counts, (size_t)n_clusters * 4},
+      {B.self_present, (size_t)n_clusters * 4},
+      {B.row_of_entry, (size_t)ne2 * 4},
+      {B.keys, (size_t)ne2 * 8},
+      {B.vals, (size_t)ne2 * 8},
+      {B.keys_sorted, (size_t)ne2 * 8},
+      {B.vals_sorted, (size_t)ne2 * 8},
+      {B.u_keys, (size_t)ne2 * 8},
+      {B.u_vals, (size_t)ne2 * 8},
+      {ctx->workspace, ctx->workspace_bytes},
+      {in.row_ptr, (size_t)(in.nv + 1) * 4},
+      {in.col, (size_t)ne2 * 4},
+      {in.w, (size_t)ne2 * 8},
+      {out.row_ptr, (size_t)(n_clusters + 1) * 4},
+      {out.col, entries * 4},
+      {out.w, entries * 8},
+  };
+  const size_t nr = sizeof(rgs) / sizeof(rgs[0]);
+  for (size_t a = 0; a < nr; ++a)
+    for (size_t b = a + 1; b < nr; ++b) {
+      const char *a0 = (const char *)rgs[a].p, *a1 = a0 + rgs[a].bytes;
+      const char *b0 = (const char *)rgs[b].p, *b1 = b0 + rgs[b].bytes;
+      if (a0 && b0 && a0 < b1 && b0 < a1) {
+        mgx_set_error(
+            "louvain coarsen: the runtime returned overlapping device "
+            "allocations (ranges %zu and %zu; ncl=%lld total=%u) — known "
+            "ROCm 7.0.x VA-placement fault at this scale, see DESIGN.md",
+            a, b, (long long)n_clusters, B.total);
+        return MGX_ERR_HIP;
+      }
+    }
+  return MGX_OK;
+}
+
+// The scatters: pairs (mirrored below the diagonal) and the missing self
+// loops into out's col/w, every write bounded by total.
+mgx_status scatter_pairs(mgx_context *ctx, const CoarsenBufs &B, const Level &out) {
+  const int64_t n_clusters = out.nv;
+  // cursor = row_ptr copy (reuse counts buffer)
+  MGX_HIP_TRY(hipMemcpyAsync(B.counts, out.row_ptr, n_clusters * 4, hipMemcpyDeviceToDevice,
+                             ctx->stream));
+  if (B.n_pairs > 0)
+    hipLaunchKernelGGL(k_pair_scatter, dim3((uint32_t)grid_for(B.n_pairs)), dim3(kBlock), 0,
+                       ctx->stream, B.n_pairs, B.u_keys, B.u_vals, n_clusters, B.total,
+                       B.counts, out.col, out.w);
+  hipLaunchKernelGGL(k_self_scatter, dim3((uint32_t)grid_for(n_clusters)), dim3(kBlock), 0,
+                     ctx->stream, n_clusters, B.self_present, B.total, B.counts, out.col,
+                     out.w);
+  MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  MGX_HIP_TRY(hipGetLastError());
+  return MGX_OK;
+}
+
+// buildNextLevelGraphOpt: aggregate (C[i] >= C[tail]) pairs, always-present
+// self loops, mirrored lower pairs. What *out owns is in `levels`, also when
+// this fails.
+mgx_status coarsen(mgx_scope &levels, const Level &in, const RowLists &R, const int32_t *C,
+                   int64_t n_clusters, Level *out) {
+  mgx_context *ctx = levels.ctx;
+  mgx_scope bufs(ctx);
+  CoarsenBufs B;
+  MGX_TRY(reduce_pairs(bufs, in, R, C, &B));
+  out->nv = n_clusters;
+  MGX_TRY(build_row_ptr(bufs, levels, n_clusters, &B, out));
+  out->ne2 = B.total;
   // col/w come from the entry-allocated ping-pong arenas when they fit
   // (they always do: total <= ne2_0 + nv_0); a direct malloc is only the
   // fallback for graphs whose first level was never arena-sized.
   const int flip = ctx->louv_flip ^= 1;
-  const size_t need_c = (size_t)(total > 0 ? total : 1) * 4;
-  const size_t need_w = (size_t)(total > 0 ? total : 1) * 8;
-  if (ctx->louv_col[flip] && need_c <= ctx->louv_col_bytes[flip] &&
-      ctx->louv_w[flip] && need_w <= ctx->louv_w_bytes[flip]) {
+  const int64_t entries = B.total > 0 ? B.total : 1;
+  if (ctx->louv_col[flip] && (size_t)entries * 4 <= ctx->louv_col_bytes[flip] &&
+      ctx->louv_w[flip] && (size_t)entries * 8 <= ctx->louv_w_bytes[flip]) {
     out->col = (int32_t *)ctx->louv_col[flip];
     out->w = (double *)ctx->louv_w[flip];
-    out->arena = true;
   } else {
-    ctx->ensure_margin(need_c + need_w);
-    MGX_HIP_TRY(mgx_hip_malloc(&out->col, need_c));
-    MGX_HIP_TRY(mgx_hip_malloc(&out->w, need_w));
+    ctx->ensure_margin((size_t)entries * 12);
+    MGX_TRY(levels.alloc_plain(&out->col, entries));
+    MGX_TRY(levels.alloc_plain(&out->w, entries));
   }
-  {
-    // ALWAYS-ON overlap gate. The box's ROCm 7.0.x runtime mis-places
-    // multi-GiB hipMallocs once the VA space is fragmented: at RMAT-25+
-    // the total-sized col/w come back overlapping five live buffers (the
-    // fit check appears to use only the low 32 bits of the size; an
-    // isolated fresh-process repro allocates the same sizes correctly).
-    // Scattering through such a mapping faults the GPU, so detect the
-    // overlap host-side and fail cleanly instead.
-    struct Rg {
-      const void *p;
-      size_t bytes;
-    } rgs[] = {
-        {counts.p, (size_t)n_clusters * 4},
-        {self_present.p, (size_t)n_clusters * 4},
-        {row_of_entry.p, (size_t)ne2 * 4},
-        {keys.p, (size_t)ne2 * 8},
-        {vals.p, (size_t)ne2 * 8},
-        {keys_sorted.p, (size_t)ne2 * 8},
-        {vals_sorted.p, (size_t)ne2 * 8},
-        {u_keys.p, (size_t)ne2 * 8},
-        {u_vals.p, (size_t)ne2 * 8},
-        {ctx->workspace, ctx->workspace_bytes},
-        {in.row_ptr, (size_t)(in.nv + 1) * 4},
-        {in.col, (size_t)ne2 * 4},
-        {in.w, (size_t)ne2 * 8},
-        {out->row_ptr, (size_t)(n_clusters + 1) * 4},
-        {out->col, (size_t)(total > 0 ? total : 1) * 4},
-        {out->w, (size_t)(total > 0 ? total : 1) * 8},
-    };
-    const size_t nr = sizeof(rgs) / sizeof(rgs[0]);
-    for (size_t a = 0; a < nr; ++a)
-      for (size_t b = a + 1; b < nr; ++b) {
-        const char *a0 = (const char *)rgs[a].p, *a1 = a0 + rgs[a].bytes;
-        const char *b0 = (const char *)rgs[b].p, *b1 = b0 + rgs[b].bytes;
-        if (a0 && b0 && a0 < b1 && b0 < a1) {
-          mgx_set_error(
-              "louvain coarsen: the runtime returned overlapping device "
-              "allocations (ranges %zu and %zu; ncl=%lld total=%u) — known "
-              "ROCm 7.0.x VA-placement fault at this scale, see DESIGN.md",
-              a, b, (long long)n_clusters, total);
-          return MGX_ERR_HIP;
-        }
-      }
-  }
-  if (louvain_trace()) {
-    // Allocator-overlap probe: the async-pool DevBufs vs the plain hipMalloc
-    // level buffers must be disjoint VA ranges.
-    struct Rng {
-      const char *name;
-      const void *p;
-      size_t bytes;
-    } rngs[] = {
-        {"counts", counts.p, (size_t)n_clusters * 4},
-        {"self_present", self_present.p, (size_t)n_clusters * 4},
-        {"row_of_entry", row_of_entry.p, (size_t)ne2 * 4},
-        {"keys", keys.p, (size_t)ne2 * 8},
-        {"vals", vals.p, (size_t)ne2 * 8},
-        {"keys_sorted", keys_sorted.p, (size_t)ne2 * 8},
-        {"vals_sorted", vals_sorted.p, (size_t)ne2 * 8},
-        {"u_keys", u_keys.p, (size_t)ne2 * 8},
-        {"u_vals", u_vals.p, (size_t)ne2 * 8},
-        {"workspace", ctx->workspace, ctx->workspace_bytes},
-        {"in.row_ptr", in.row_ptr, (size_t)(in.nv + 1) * 4},
-        {"in.col", in.col, (size_t)ne2 * 4},
-        {"in.w", in.w, (size_t)ne2 * 8},
-        {"row_ptr", out->row_ptr, (size_t)(n_clusters + 1) * 4},
-        {"col", out->col, (size_t)(total > 0 ? total : 1) * 4},
-        {"w", out->w, (size_t)(total > 0 ? total : 1) * 8},
-    };
-    for (auto &r : rngs)
-      MGX_LTRACE("coarsen buf %-12s [%p, %p)", r.name, r.p,
-                 (const void *)((const char *)r.p + r.bytes));
-    for (size_t a = 0; a < sizeof(rngs) / sizeof(rngs[0]); ++a)
-      for (size_t b = a + 1; b < sizeof(rngs) / sizeof(rngs[0]); ++b) {
-        const char *a0 = (const char *)rngs[a].p, *a1 = a0 + rngs[a].bytes;
-        const char *b0 = (const char *)rngs[b].p, *b1 = b0 + rngs[b].bytes;
-        if (a0 < b1 && b0 < a1)
-          MGX_LTRACE("coarsen ALIAS %s overlaps %s", rngs[a].name, rngs[b].name);
-      }
-  }
-  // cursor = row_ptr copy (reuse counts buffer)
-  MGX_HIP_TRY(hipMemcpyAsync(counts.p, out->row_ptr, n_clusters * 4,
-                             hipMemcpyDeviceToDevice, ctx->stream));
-  MGX_LTRACE("coarsen pair_scatter");
-  if (n_pairs > 0)
-    hipLaunchKernelGGL(k_pair_scatter, dim3((uint32_t)grid_for(n_pairs)), dim3(kBlock), 0,
-                       ctx->stream, n_pairs, u_keys.as<uint64_t>(), u_vals.as<double>(),
-                       n_clusters, total, counts.as<uint32_t>(), out->col, out->w);
-  MGX_LTRACE("coarsen self_scatter");
-  hipLaunchKernelGGL(k_self_scatter, dim3((uint32_t)grid_for(n_clusters)), dim3(kBlock), 0,
-                     ctx->stream, n_clusters, self_present.as<uint32_t>(), total,
-                     counts.as<uint32_t>(), out->col, out->w);
-  MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  MGX_HIP_TRY(hipGetLastError());
-  MGX_LTRACE("coarsen done");
-  return MGX_OK;
+  MGX_TRY(coarsen_gates(ctx, in, B, *out));
+  return scatter_pairs(ctx, B, *out);
 }
 
-void free_level(Level *L, bool own) {
-  if (!own) return;
-  if (L->row_ptr) (void)hipFree(L->row_ptr);
-  if (!L->arena) {
-    if (L->col) (void)hipFree(L->col);
-    if (L->w) (void)hipFree(L->w);
-  }
-  L->row_ptr = nullptr;
-  L->col = nullptr;
-  L->w = nullptr;
+// Frees what `levels` owns of L: a coarse level's row_ptr, and its col/w where
+// they are not the context arenas. Level 0 is the graph's; nothing of it is.
+void free_level(mgx_scope &levels, Level *L) {
+  levels.release(L->row_ptr);
+  levels.release(L->col);
+  levels.release(L->w);
+  *L = Level{};
 }
 
 __global__ void k_compose(int64_t nv, int32_t *c_orig, const int32_t *C) {
@@ -1417,7 +1046,6 @@ mgx_status mgx_louvain_impl(mgx_context *ctx, mgx_graph *g, double threshold,
   }
   if (nv0 == 0 || g->n_edges == 0) return MGX_OK;
 
-  // Level 0: widen weights to fp64 (unweighted graphs: all 1.0).
   Level L;
   L.nv = nv0;
   L.row_ptr = g->sym_row_ptr;
@@ -1445,81 +1073,59 @@ mgx_status mgx_louvain_impl(mgx_context *ctx, mgx_graph *g, double threshold,
       }
     }
   }
-  DevBuf w0;
-  MGX_HIP_TRY(w0.alloc(ctx, L.ne2 * 8));
+  // bufs: the call's own buffers. levels: the coarse levels (free_level).
+  mgx_scope bufs(ctx), levels(ctx);
+  // Level 0: widen weights to fp64 (unweighted graphs: all 1.0).
+  MGX_TRY(bufs.alloc(&L.w, L.ne2));
   if (g->sym_w) {
-    hipLaunchKernelGGL(k_f32_to_f64, dim3((uint32_t)grid_for(L.ne2)), dim3(kBlock), 0,
-                       ctx->stream, L.ne2, g->sym_w, (double *)w0.p);
+    hipLaunchKernelGGL((mgx_k_widen<float, double>), dim3((uint32_t)grid_for(L.ne2)),
+                       dim3(kBlock), 0, ctx->stream, L.ne2, g->sym_w, L.w);
   } else {
-    struct K {
-      static __global__ void fill1(int64_t n, double *p) {
-        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-             i += (int64_t)gridDim.x * blockDim.x)
-          p[i] = 1.0;
-      }
-    };
-    hipLaunchKernelGGL(K::fill1, dim3((uint32_t)grid_for(L.ne2)), dim3(kBlock), 0,
-                       ctx->stream, L.ne2, (double *)w0.p);
+    hipLaunchKernelGGL(mgx_k_fill<double>, dim3((uint32_t)grid_for(L.ne2)), dim3(kBlock), 0,
+                       ctx->stream, L.ne2, 1.0, L.w);
   }
-  L.w = (double *)w0.p;
-  bool own_level = false;
-
-  DevBuf c_orig_d, c_level;
-  MGX_HIP_TRY(c_orig_d.alloc(ctx, nv0 * 4));
+  int32_t *c_orig = nullptr;
+  MGX_TRY(bufs.alloc(&c_orig, nv0));
   hipLaunchKernelGGL(mgx_k_fill<int32_t>, dim3((uint32_t)grid_for(nv0)), dim3(kBlock), 0,
-                     ctx->stream, nv0, -1, c_orig_d.as<int32_t>());
+                     ctx->stream, nv0, -1, c_orig);
 
   double prev_mod = -1.0, curr_mod = -1.0;
   int64_t phase = 1, tot_itr = 0;
-  mgx_status status = MGX_OK;
   while (true) {
-    DevBuf C;
-    if (C.alloc(ctx, L.nv * 4) != hipSuccess) {
-      status = MGX_ERR_OUT_OF_MEMORY;
-      break;
-    }
+    mgx_scope phase_bufs(ctx);
+    int32_t *C = nullptr;
+    RowLists rows;
+    MGX_TRY(phase_bufs.alloc(&C, L.nv));
+    MGX_TRY(build_row_lists(phase_bufs, L, &rows));
     prev_mod = curr_mod;
     int64_t iters = 0;
-    MGX_LDBG(ctx, "phase=%lld level nv=%lld ne2=%lld", (long long)phase, (long long)L.nv,
-             (long long)L.ne2);
-    status = louvain_level(ctx, L, prev_mod, threshold, C.as<int32_t>(), &curr_mod, &iters);
-    if (status != MGX_OK) break;
+    MGX_TRY(louvain_level(ctx, L, rows, prev_mod, threshold, C, &curr_mod, &iters));
     tot_itr += iters;
     int64_t n_clusters = 0;
-    status = renumber(ctx, C.as<int32_t>(), L.nv, &n_clusters);
-    if (status != MGX_OK) break;
+    MGX_TRY(renumber(ctx, C, L.nv, &n_clusters));
     if (phase == 1) {
-      MGX_HIP_TRY(hipMemcpyAsync(c_orig_d.p, C.p, nv0 * 4, hipMemcpyDeviceToDevice,
-                                 ctx->stream));
+      MGX_HIP_TRY(hipMemcpyAsync(c_orig, C, nv0 * 4, hipMemcpyDeviceToDevice, ctx->stream));
     } else {
       hipLaunchKernelGGL(k_compose, dim3((uint32_t)grid_for(nv0)), dim3(kBlock), 0,
-                         ctx->stream, nv0, c_orig_d.as<int32_t>(), C.as<int32_t>());
+                         ctx->stream, nv0, c_orig, C);
     }
     if (phase > 200 || tot_itr > 100000) break;
-    if ((curr_mod - prev_mod) > threshold) {
-      Level next;
-      MGX_LDBG(ctx, "coarsen from nv=%lld to %lld", (long long)L.nv,
-               (long long)n_clusters);
-      status = coarsen(ctx, L, C.as<int32_t>(), n_clusters, &next);
-      free_level(&L, own_level);
-      if (status != MGX_OK) break;
-      L = next;
-      own_level = true;
-      ++phase;
-    } else {
-      break;
-    }
+    if (!((curr_mod - prev_mod) > threshold)) break;
+    Level next;
+    MGX_TRY(coarsen(levels, L, rows, C, n_clusters, &next));
+    free_level(levels, &L);
+    L = next;
+    ++phase;
   }
-  free_level(&L, own_level);
-  if (status != MGX_OK) return status;
+  free_level(levels, &L);
 
   // Download.
-  DevBuf wide;
-  MGX_HIP_TRY(wide.alloc(ctx, nv0 * 8));
+  int64_t *wide = nullptr;
+  MGX_TRY(bufs.alloc(&wide, nv0));
   hipLaunchKernelGGL((mgx_k_widen<int32_t, int64_t>), dim3((uint32_t)grid_for(nv0)),
-                     dim3(kBlock), 0, ctx->stream, nv0, c_orig_d.as<int32_t>(), wide.as<int64_t>());
+                     dim3(kBlock), 0, ctx->stream, nv0, c_orig, wide);
   if (out_community) {
-    MGX_HIP_TRY(hipMemcpyAsync(out_community, wide.p, nv0 * 8, hipMemcpyDeviceToHost,
+    MGX_HIP_TRY(hipMemcpyAsync(out_community, wide, nv0 * 8, hipMemcpyDeviceToHost,
                                ctx->stream));
   }
   MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
