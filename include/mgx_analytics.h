@@ -108,6 +108,10 @@ int64_t mgx_graph_in_zero_rows(const mgx_graph *g);
 /* Heavy rows that PageRank sweeps XCD-striped (memory layout
  * lever 4), or -1 when the graph was not built in that layout. */
 int64_t mgx_graph_xcd_heavy_rows(const mgx_graph *g);
+/* Length in ints of the stripe-major column stream the striped sweep reads
+ * (lever 6), or -1 when the graph has none (not striped, no heavy rows,
+ * MGX_PR_XCD_STREAM=0 at build, or a length past uint32). */
+int64_t mgx_graph_xcd_stream_ints(const mgx_graph *g);
 
 /* ---- PageRank (replaces pagerank_alg::ParallelIterativePageRank,
  *      algorithm/pagerank.cpp:194-242, and the pagerank.so module path) --- */

@@ -14,6 +14,7 @@
 #include "../../include/mgx_graphgen.h"
 #include "mgx_device.h"
 #include "mgx_xcd_deal.h"
+#include "mgx_xcd_stream.h"
 
 namespace {
 
@@ -439,6 +440,158 @@ __global__ void k_xcd_deal(int64_t n, const int32_t *order_sorted, const uint32_
   }
 }
 
+// The 32 (stripe, section) lists of the striped launch in the order it reads
+// them: list k = x * 4 + (3 - sec). Segment i of list k is item first + i of
+// the stream build's allotment and offset arrays.
+struct xcd_stream_lists {
+  const int32_t *rows[kXcdStripes * 4];
+  int64_t n[kXcdStripes * 4];
+  int64_t first[kXcdStripes * 4 + 1];
+  uint32_t base[kXcdStripes];  // first int of the stripe's window (fill pass)
+};
+
+// allot[item] = ints allotted to the item's segment (mgx_xcd_stream.h).
+__global__ void k_xcd_stream_allot(xcd_stream_lists L, const uint32_t *xptr, int64_t nH,
+                                   uint32_t *allot) {
+  for (int k = 0; k < kXcdStripes * 4; ++k) {
+    const int x = k / 4, sec = 3 - k % 4;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < L.n[k];
+         i += (int64_t)gridDim.x * blockDim.x) {
+      const int32_t slot = L.rows[k][i];
+      const uint32_t lo = xptr[(size_t)x * nH + slot];
+      const uint32_t hi = xptr[(size_t)(x + 1) * nH + slot];
+      allot[L.first[k] + i] = mgx_xcd_seg_allot(lo, hi - lo, mgx_xcd_seg_aligned(sec));
+    }
+  }
+}
+
+// Copy every segment to its place in the stream, zero the padding of its
+// allotment and record its bounds. rel[item] is the start of the item's
+// allotment within its stripe's window. A segment is copied by as many lanes
+// as the sweep gives it.
+__global__ void __launch_bounds__(kBlock)
+k_xcd_stream_fill(xcd_stream_lists L, const uint32_t *xptr, int64_t nH, const int32_t *col,
+                  const uint32_t *rel, int32_t *scol, uint32_t *slo, uint32_t *shi) {
+  for (int x = 0; x < kXcdStripes; ++x) {
+    auto section = [&](auto lanes, int sec) {
+      constexpr int LANES = decltype(lanes)::value;
+      const int k = x * 4 + (3 - sec);
+      const bool aligned = mgx_xcd_seg_aligned(sec);
+      for_row_steps<LANES>(
+          L.rows[k], L.n[k], blockIdx.x, gridDim.x, [&](const int32_t *rowp, bool live, int sub) {
+            if (!live) return;
+            const int32_t slot = *rowp;
+            const int64_t item = L.first[k] + (rowp - L.rows[k]);
+            const uint32_t lo = xptr[(size_t)x * nH + slot];
+            const uint32_t len = xptr[(size_t)(x + 1) * nH + slot] - lo;
+            const uint32_t pos = L.base[x] + rel[item];
+            const uint32_t start = mgx_xcd_seg_start(pos, lo, aligned);
+            for (uint32_t j = sub; j < len; j += LANES) scol[start + j] = col[lo + j];
+            if (sub == 0) {
+              slo[(size_t)x * nH + slot] = start;
+              shi[(size_t)x * nH + slot] = start + len;
+              const uint32_t end = pos + mgx_xcd_seg_allot(lo, len, aligned);
+              for (uint32_t j = pos; j < start; ++j) scol[j] = 0;
+              for (uint32_t j = start + len; j < end; ++j) scol[j] = 0;
+            }
+          });
+    };
+    section(std::integral_constant<int, 256>{}, 3);
+    section(std::integral_constant<int, 64>{}, 2);
+    section(std::integral_constant<int, 16>{}, 1);
+    section(std::integral_constant<int, 4>{}, 0);
+  }
+}
+
+// The stripe-major column stream of the striped launch (g->xcd_scol, lever 6).
+mgx_status build_xcd_stream(mgx_context *ctx, mgx_graph *g) {
+  if (const char *e = getenv("MGX_PR_XCD_STREAM")) {
+    if (*e && atoi(e) == 0) return MGX_OK;
+  }
+  const int64_t nH = g->xcd_nH;
+  xcd_stream_lists L = {};
+  int64_t items = 0, aligned_items = 0;
+  for (int x = 0; x < kXcdStripes; ++x) {
+    mgx_bin_sections S;
+    (void)mgx_fill_sections(g->xcd_bins[x], &S);
+    for (int sec = 3; sec >= 0; --sec) {
+      const int k = x * 4 + (3 - sec);
+      L.rows[k] = S.rows + S.off[sec];
+      L.n[k] = S.n[sec];
+      L.first[k] = items;
+      items += S.n[sec];
+      if (mgx_xcd_seg_aligned(sec)) aligned_items += S.n[sec];
+    }
+  }
+  L.first[kXcdStripes * 4] = items;
+  if (items == 0) return MGX_OK;
+  // Bounds are uint32. The segments hold at most in_edges ints, an aligned
+  // allotment adds at most 6 and a stripe's window at most kXcdStreamAlign - 1:
+  // when that bound fits, no offset below can wrap. A graph past it (a stream
+  // within a few percent of 2^32 ints) keeps reading in_col.
+  const uint64_t most = (uint64_t)g->in_edges + 6ull * (uint64_t)aligned_items +
+                        (uint64_t)kXcdStripes * kXcdStreamAlign;
+  if (most > 0xFFFFFFFFull) return MGX_OK;
+
+  mgx_scope bufs(ctx);
+  uint32_t *allot = nullptr, *rel = nullptr;
+  MGX_TRY(bufs.alloc(&allot, items));
+  MGX_TRY(bufs.alloc(&rel, items));
+  hipLaunchKernelGGL(k_xcd_stream_allot, dim3(grid_for(items)), dim3(kBlock), 0, ctx->stream, L,
+                     (const uint32_t *)g->xcd_ptr, nH, allot);
+  // One exclusive scan per stripe; a stripe's length is its last offset plus
+  // its last allotment.
+  uint32_t last_rel[kXcdStripes] = {0}, last_allot[kXcdStripes] = {0};
+  for (int x = 0; x < kXcdStripes; ++x) {
+    const int64_t first = L.first[x * 4], n = L.first[x * 4 + 4] - first;
+    if (n == 0) continue;
+    MGX_TRY(mgx_with_temp(ctx, "column stream scan", [&](void *tmp, size_t &bytes) {
+      return rocprim::exclusive_scan(tmp, bytes, allot + first, rel + first, 0u, n,
+                                     rocprim::plus<uint32_t>(), ctx->stream);
+    }));
+    MGX_HIP_TRY(hipMemcpyAsync(&last_rel[x], rel + first + n - 1, 4, hipMemcpyDeviceToHost,
+                               ctx->stream));
+    MGX_HIP_TRY(hipMemcpyAsync(&last_allot[x], allot + first + n - 1, 4, hipMemcpyDeviceToHost,
+                               ctx->stream));
+  }
+  MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  uint64_t end[kXcdStripes], total = 0;
+  for (int x = 0; x < kXcdStripes; ++x) {
+    L.base[x] = (uint32_t)total;
+    end[x] = total + last_rel[x] + last_allot[x];
+    total = mgx_xcd_stream_round(end[x]);
+  }
+  if (total > most) {  // cannot be: the scans would contradict the bound above
+    mgx_set_error("column stream: %llu ints exceed the bound %llu",
+                  (unsigned long long)total, (unsigned long long)most);
+    return MGX_ERR_TOO_LARGE;
+  }
+
+  MGX_HIP_TRY(mgx_hip_malloc(&g->xcd_scol, (size_t)total * sizeof(int32_t)));
+  MGX_HIP_TRY(mgx_hip_malloc(&g->xcd_slo, (size_t)kXcdStripes * nH * sizeof(uint32_t)));
+  MGX_HIP_TRY(mgx_hip_malloc(&g->xcd_shi, (size_t)kXcdStripes * nH * sizeof(uint32_t)));
+  // Empty segments are in no list: their bounds stay 0 and nothing reads them.
+  MGX_HIP_TRY(hipMemsetAsync(g->xcd_slo, 0, (size_t)kXcdStripes * nH * sizeof(uint32_t),
+                             ctx->stream));
+  MGX_HIP_TRY(hipMemsetAsync(g->xcd_shi, 0, (size_t)kXcdStripes * nH * sizeof(uint32_t),
+                             ctx->stream));
+  for (int x = 0; x < kXcdStripes; ++x) {  // the gap up to the next window
+    const uint64_t next = mgx_xcd_stream_round(end[x]);
+    if (next > end[x]) {
+      MGX_HIP_TRY(hipMemsetAsync(g->xcd_scol + end[x], 0, (size_t)(next - end[x]) * sizeof(int32_t),
+                                 ctx->stream));
+    }
+  }
+  hipLaunchKernelGGL(k_xcd_stream_fill, dim3(grid_for(items, 8192)), dim3(kBlock), 0,
+                     ctx->stream, L, (const uint32_t *)g->xcd_ptr, nH,
+                     (const int32_t *)g->in_col, (const uint32_t *)rel, g->xcd_scol, g->xcd_slo,
+                     g->xcd_shi);
+  MGX_HIP_TRY(hipGetLastError());
+  MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  g->xcd_stream_ints = (int64_t)total;
+  return MGX_OK;
+}
+
 // Heavy-row stripe view for the XCD-striped PageRank sweep (g->xcd).
 mgx_status build_xcd_view(mgx_context *ctx, mgx_graph *g) {
   // Heavy rows are whole sections of bins_in, so the slot -> row list is the
@@ -474,7 +627,7 @@ mgx_status build_xcd_view(mgx_context *ctx, mgx_graph *g) {
   MGX_HIP_TRY(hipMemcpyAsync(g->xcd_sec, secs, sizeof(secs), hipMemcpyHostToDevice,
                              ctx->stream));
   MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  return MGX_OK;
+  return build_xcd_stream(ctx, g);
 }
 }  // namespace
 

@@ -426,6 +426,9 @@ extern "C" mgx_status mgx_graph_destroy(mgx_context *ctx, mgx_graph *g) {
   }
   if (g->xcd_ptr) (void)hipFree(g->xcd_ptr);
   if (g->xcd_sec) (void)hipFree(g->xcd_sec);
+  if (g->xcd_scol) (void)hipFree(g->xcd_scol);
+  if (g->xcd_slo) (void)hipFree(g->xcd_slo);
+  if (g->xcd_shi) (void)hipFree(g->xcd_shi);
   for (int i = 0; i < 8; ++i) {
     if (g->xcd_bins[i].rows) (void)hipFree(g->xcd_bins[i].rows);
   }
@@ -445,6 +448,9 @@ extern "C" double mgx_graph_build_ms(const mgx_graph *g) { return g->build_ms; }
 extern "C" int64_t mgx_graph_in_zero_rows(const mgx_graph *g) { return g->bins_in.n_zero; }
 extern "C" int64_t mgx_graph_xcd_heavy_rows(const mgx_graph *g) {
   return g->xcd ? g->xcd_nH : -1;
+}
+extern "C" int64_t mgx_graph_xcd_stream_ints(const mgx_graph *g) {
+  return g->xcd_scol ? g->xcd_stream_ints : -1;
 }
 
 extern "C" mgx_status mgx_wcc(mgx_context *ctx, mgx_graph *g, int64_t *out_component,

@@ -235,6 +235,19 @@ struct mgx_graph {
   uint32_t *xcd_ptr = nullptr;     // [9 * nH]
   mgx_bins xcd_bins[8];
   struct mgx_bin_sections *xcd_sec = nullptr;  // [8] device: xcd_bins as launch sections
+  // Stripe-major column stream (lever 6, mgx_xcd_stream.h): the columns of the
+  // non-empty segments copied into the order the striped launch reads them,
+  // so that each stripe reads one contiguous window and shares no cache line
+  // with another. Segment (x, s) is xcd_scol[xcd_slo[x*nH + s] ..
+  // xcd_shi[x*nH + s]), the same ids as its in_col range and at the same
+  // offset mod 4 where the section's vector body depends on it.
+  // xcd_stream_ints is the stream's length, -1 when none was built
+  // (MGX_PR_XCD_STREAM=0, or a length past uint32): the launch then reads
+  // in_col through xcd_ptr.
+  int32_t *xcd_scol = nullptr;
+  uint32_t *xcd_slo = nullptr;  // [8 * nH]
+  uint32_t *xcd_shi = nullptr;  // [8 * nH]
+  int64_t xcd_stream_ints = -1;
 
   // Deduplicated view of the out-CSR (similarity.hip), built at the first
   // similarity call. When the out-CSR has no repeated (src, dst) both

@@ -13,9 +13,10 @@
 // DESIGN.md "Memory layout levers" item 4): the heavy rows in one launch
 // whose blocks each gather from one eighth of contrib, the light rows in the
 // fused kernel above, and a finish kernel over the heavy rows. The striped
-// launch keeps the hottest sources of its stripe in LDS (lever 5). From a
-// run's third sweep on, the rows of in-degree 0 are left out: both ping-pong
-// buffers already hold their values.
+// launch keeps the hottest sources of its stripe in LDS (lever 5) and reads
+// its column ids from a stripe-major copy of the heavy rows' columns (lever
+// 6). From a run's third sweep on, the rows of in-degree 0 are left out: both
+// ping-pong buffers already hold their values.
 //
 // Parity bar (tests/test_gpu_pagerank.py): |r_gpu - r_cpu|inf <= 1e-6 vs the
 // fp64 oracle after equal iterations, post sum-normalize.
@@ -202,11 +203,11 @@ __global__ void __launch_bounds__(kBlock) k_pr_sweep(PrArgs A) {
 // partial[x * nH + slot]; k_pr_finish_heavy combines them. No block reads
 // what another wrote: a different placement changes the speed only.
 struct PrXcdArgs {
-  const int32_t *col;
+  const int32_t *col;             // xcd_scol, or in_col where there is no stream
   const float *contrib_old;
   double *partial;                // [8 * nH], stripe-major
   const mgx_bin_sections *sec;    // [8] device: stripe x's sections over slots
-  const uint32_t *xptr;           // [9 * nH] stripe boundaries by slot
+  const uint32_t *lo, *hi;        // [8 * nH] each: segment (x, slot) is col[lo .. hi)
   int64_t nH;
   int64_t V;
   uint32_t hot_k;                 // HOT: floats of dynamic LDS per block
@@ -225,8 +226,8 @@ __global__ void __launch_bounds__(THREADS) k_pr_sweep_xcd(PrXcdArgs X) {
   const mgx_bin_sections &S = X.sec[x];
   PrArgs A;  // only what pr_row_sum reads
   A.col = X.col;
-  A.sp_lo = X.xptr + (size_t)x * X.nH;
-  A.sp_hi = A.sp_lo + X.nH;
+  A.sp_lo = X.lo + (size_t)x * X.nH;
+  A.sp_hi = X.hi + (size_t)x * X.nH;
   double *out = X.partial + (size_t)x * X.nH;
   const int64_t block = blockIdx.x / kXcdStripes;
   const int64_t nblocks = gridDim.x / kXcdStripes;
@@ -348,11 +349,21 @@ mgx_status queue_xcd_sweep(mgx_pagerank_run *run, PrArgs A) {
   const int64_t nH = g->xcd_nH;
   if (nH > 0) {
     PrXcdArgs X;
-    X.col = g->in_col;
+    // The stripe-major column stream where the build made one (lever 6): the
+    // same ids at the same offsets mod 4, so the same additions in the same
+    // order. Otherwise the segments of in_col between the stripe boundaries.
+    if (g->xcd_scol) {
+      X.col = g->xcd_scol;
+      X.lo = g->xcd_slo;
+      X.hi = g->xcd_shi;
+    } else {
+      X.col = g->in_col;
+      X.lo = g->xcd_ptr;
+      X.hi = g->xcd_ptr + nH;
+    }
     X.contrib_old = A.contrib_old;
     X.partial = run->d_partial;
     X.sec = g->xcd_sec;
-    X.xptr = g->xcd_ptr;
     X.nH = nH;
     X.V = g->n_vertices;
     X.hot_k = (uint32_t)run->xcd_lds_floats;

@@ -103,6 +103,7 @@ class Native:
         self.lib.mgx_graph_num_edges.restype = ctypes.c_int64
         self.lib.mgx_graph_local_edges.restype = ctypes.c_int64
         self.lib.mgx_graph_xcd_heavy_rows.restype = ctypes.c_int64
+        self.lib.mgx_graph_xcd_stream_ints.restype = ctypes.c_int64
         self.lib.mgx_graph_in_zero_rows.restype = ctypes.c_int64
         self.lib.mgx_pagerank_xcd_lds_floats.restype = ctypes.c_int64
 
@@ -192,6 +193,11 @@ class Native:
     def graph_xcd_heavy_rows(self, g):
         """Rows PageRank sweeps XCD-striped, or -1 when that layout is off."""
         return self.lib.mgx_graph_xcd_heavy_rows(g)
+
+    def graph_xcd_stream_ints(self, g):
+        """Ints of the striped sweep's stripe-major column stream, or -1 when
+        the graph has none."""
+        return self.lib.mgx_graph_xcd_stream_ints(g)
 
     def graph_in_zero_rows(self, g):
         """Rows with no in-edges, left out of the steady-state PageRank sweep."""
