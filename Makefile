@@ -26,7 +26,7 @@ build/%.o: %.cpp memgraph_amd/csrc/mgx_internal.h include/mgx_analytics.h
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-build/%.o: %.hip memgraph_amd/csrc/mgx_internal.h memgraph_amd/csrc/mgx_device.h memgraph_amd/csrc/mgx_comm_table.h memgraph_amd/csrc/mgx_xcd_deal.h memgraph_amd/csrc/mgx_xcd_stream.h include/mgx_analytics.h include/mgx_graphgen.h
+build/%.o: %.hip memgraph_amd/csrc/mgx_internal.h memgraph_amd/csrc/mgx_device.h memgraph_amd/csrc/mgx_comm_table.h memgraph_amd/csrc/mgx_xcd_deal.h memgraph_amd/csrc/mgx_xcd_stream.h memgraph_amd/csrc/mgx_online.h memgraph_amd/csrc/mgx_slot_table.h include/mgx_analytics.h include/mgx_graphgen.h
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

@@ -45,29 +45,31 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "mgx_device.h"
+#include "mgx_online.h"
 
 namespace {
 
 constexpr uint32_t kBigRow = 256;  // >=: block-per-row gather
 
-struct KOnState {
-  std::unordered_map<int64_t, int32_t> mg2slot;
-  std::vector<int64_t> slot2mg;
-  std::vector<uint8_t> alive_h;  // slot present in the centrality maps
+constexpr int64_t kFirstSlots = 256;  // first capacity of the slot-space arrays
 
-  // per-iteration history (device, slot space, capacity slots_cap)
-  std::vector<double *> omega, cent;
-  double *lr = nullptr, *ur = nullptr;
-  uint8_t *d_active = nullptr;
-  std::vector<uint8_t> active_h;  // mirrors the reference's std::set
-  int64_t slots_cap = 0;
+struct KOnState {
+  mgx_slot_table slots;  // alive: slot present in the centrality maps
+
+  // per-iteration history (device, slot space, capacity >= slots_cap())
+  std::vector<mgx_dev_array<double>> omega, cent;
+  mgx_dev_array<double> lr, ur;
+  mgx_dev_array<uint8_t> d_active;
+  // mirrors the reference's std::set; sized to the slot table where it is used
+  std::vector<uint8_t> active_h;
+  // What every slot-space array holds at least: kon_grow_slots grows d_active last.
+  int64_t slots_cap() const { return d_active.cap; }
   int64_t iteration = 0;
   double alpha = 0.2, eps = 1e-2;
   bool initialized = false;
 };
 
-KOnState g_k;
+KOnState &g_k = *new KOnState;  // never deleted: see mgx_online.h
 
 // ---- kernels -------------------------------------------------------------
 
@@ -279,120 +281,46 @@ __global__ void k_gather_out(int64_t V, const int32_t *dense2slot, const double 
 
 // ---- host helpers --------------------------------------------------------
 
-void kon_free_state() {
-  for (auto p : g_k.omega) (void)hipFree(p);
-  for (auto p : g_k.cent) (void)hipFree(p);
-  if (g_k.lr) (void)hipFree(g_k.lr);
-  if (g_k.ur) (void)hipFree(g_k.ur);
-  if (g_k.d_active) (void)hipFree(g_k.d_active);
-  g_k = KOnState{};
-}
-
-int32_t kon_slot(int64_t mg) {
-  auto it = g_k.mg2slot.find(mg);
-  if (it != g_k.mg2slot.end()) return it->second;
-  const int32_t s = (int32_t)g_k.slot2mg.size();
-  g_k.mg2slot.emplace(mg, s);
-  g_k.slot2mg.push_back(mg);
-  g_k.alive_h.push_back(0);
-  g_k.active_h.push_back(0);
-  return s;
-}
-
 mgx_status kon_grow_slots(mgx_context *ctx, int64_t need) {
-  if (need <= g_k.slots_cap) return MGX_OK;
-  int64_t cap = g_k.slots_cap > 0 ? g_k.slots_cap : 256;
-  while (cap < need) cap *= 2;
-  auto grow = [&](double **p, double init) -> mgx_status {
-    mgx_scope grown(ctx);
-    double *np = nullptr;
-    MGX_TRY(grown.alloc_plain(&np, cap));
-    hipLaunchKernelGGL(mgx_k_fill<double>, dim3((uint32_t)grid_for(cap)), dim3(kBlock), 0,
-                       ctx->stream, cap, init, np);
-    if (*p && g_k.slots_cap > 0) {
-      MGX_HIP_TRY(hipMemcpyAsync(np, *p, g_k.slots_cap * 8, hipMemcpyDeviceToDevice,
-                                 ctx->stream));
-    }
-    if (*p) {
-      MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-      (void)hipFree(*p);
-    }
-    *p = grown.give_up(np);
-    return MGX_OK;
+  auto grow = [&](mgx_dev_array<double> &a, double init) {
+    return a.ensure(ctx, need, kFirstSlots, a.cap, mgx_fill_value(ctx, init));
   };
   for (size_t i = 0; i < g_k.omega.size(); ++i)
-    MGX_TRY(grow(&g_k.omega[i], i == 0 ? 1.0 : 0.0));
-  for (size_t i = 0; i < g_k.cent.size(); ++i) MGX_TRY(grow(&g_k.cent[i], 0.0));
-  MGX_TRY(grow(&g_k.lr, 0.0));
-  MGX_TRY(grow(&g_k.ur, 0.0));
-  {
-    mgx_scope grown(ctx);
-    uint8_t *na = nullptr;
-    MGX_TRY(grown.alloc_plain(&na, cap));
-    MGX_HIP_TRY(hipMemsetAsync(na, 0, cap, ctx->stream));
-    if (g_k.d_active && g_k.slots_cap > 0) {
-      MGX_HIP_TRY(hipMemcpyAsync(na, g_k.d_active, g_k.slots_cap,
-                                 hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (g_k.d_active) (void)hipFree(g_k.d_active);
-    g_k.d_active = grown.give_up(na);
-  }
-  g_k.slots_cap = cap;
-  return MGX_OK;
+    MGX_TRY(grow(g_k.omega[i], i == 0 ? 1.0 : 0.0));
+  for (auto &c : g_k.cent) MGX_TRY(grow(c, 0.0));
+  MGX_TRY(grow(g_k.lr, 0.0));
+  MGX_TRY(grow(g_k.ur, 0.0));
+  return g_k.d_active.ensure(ctx, need, kFirstSlots, g_k.d_active.cap, mgx_fill_zero(ctx));
 }
 
 mgx_status kon_add_iteration(mgx_context *ctx, double omega_init) {
-  mgx_scope fresh(ctx);
-  double *w = nullptr, *c = nullptr;
-  MGX_TRY(fresh.alloc_plain(&w, g_k.slots_cap));
-  MGX_TRY(fresh.alloc_plain(&c, g_k.slots_cap));
-  hipLaunchKernelGGL(mgx_k_fill<double>, dim3((uint32_t)grid_for(g_k.slots_cap)),
-                     dim3(kBlock), 0, ctx->stream, g_k.slots_cap, omega_init, w);
-  hipLaunchKernelGGL(mgx_k_fill<double>, dim3((uint32_t)grid_for(g_k.slots_cap)),
-                     dim3(kBlock), 0, ctx->stream, g_k.slots_cap, 0.0, c);
-  g_k.omega.push_back(fresh.give_up(w));
-  g_k.cent.push_back(fresh.give_up(c));
+  mgx_dev_array<double> w, c;
+  MGX_TRY(w.ensure(ctx, g_k.slots_cap(), kFirstSlots, 0, mgx_fill_value(ctx, omega_init)));
+  MGX_TRY(c.ensure(ctx, g_k.slots_cap(), kFirstSlots, 0, mgx_fill_value(ctx, 0.0)));
+  g_k.omega.push_back(std::move(w));
+  g_k.cent.push_back(std::move(c));
   return MGX_OK;
 }
 
 struct KMaps {
+  mgx_scope own;                  // of the device lists
   int32_t *dense2slot = nullptr;  // device
   std::vector<int32_t> d2s_h;
   int64_t V = 0;
   // dense row lists by in-degree bin
   int32_t *small_rows = nullptr, *big_rows = nullptr;
   int64_t n_small = 0, n_big = 0;
-  ~KMaps() {
-    if (dense2slot) (void)hipFree(dense2slot);
-    if (small_rows) (void)hipFree(small_rows);
-    if (big_rows) (void)hipFree(big_rows);
-  }
+  explicit KMaps(mgx_context *ctx) : own(ctx) {}
 };
 
-mgx_status kon_build_maps(mgx_context *ctx, mgx_graph *g, const int64_t *dense_to_mg,
-                          bool create, KMaps *m, bool *all_known) {
+// Slots (created where unseen) and in-degree bins for the graph's vertices.
+mgx_status kon_build_maps(mgx_graph *g, const int64_t *dense_to_mg, KMaps *m) {
+  mgx_context *ctx = m->own.ctx;
   const int64_t V = g ? g->n_vertices : 0;
   m->V = V;
-  m->d2s_h.assign(V > 0 ? V : 1, -1);
-  bool known = true;
-  for (int64_t v = 0; v < V; ++v) {
-    if (create) {
-      m->d2s_h[v] = kon_slot(dense_to_mg[v]);
-    } else {
-      auto it = g_k.mg2slot.find(dense_to_mg[v]);
-      if (it == g_k.mg2slot.end() || !g_k.alive_h[it->second]) {
-        known = false;
-        m->d2s_h[v] = -1;
-      } else {
-        m->d2s_h[v] = it->second;
-      }
-    }
-  }
-  if (all_known) *all_known = known;
-  MGX_HIP_TRY(mgx_hip_malloc(&m->dense2slot, (V > 0 ? V : 1) * 4));
-  MGX_HIP_TRY(hipMemcpyAsync(m->dense2slot, m->d2s_h.data(), (V > 0 ? V : 1) * 4,
-                             hipMemcpyHostToDevice, ctx->stream));
+  g_k.slots.map_dense(dense_to_mg, V, /*create=*/true, &m->d2s_h, nullptr);
+  g_k.active_h.resize(g_k.slots.size(), 0);
+  MGX_TRY(mgx_upload_i32(m->own, m->d2s_h, &m->dense2slot));
   // in-degree bins from the in-CSR (host-side row_ptr copy)
   if (V > 0 && g && g->in_row_ptr) {
     std::vector<uint32_t> rp(V + 1);
@@ -407,15 +335,8 @@ mgx_status kon_build_maps(mgx_context *ctx, mgx_graph *g, const int64_t *dense_t
     }
     m->n_small = (int64_t)sm.size();
     m->n_big = (int64_t)bg.size();
-    MGX_HIP_TRY(mgx_hip_malloc(&m->small_rows, (m->n_small > 0 ? m->n_small : 1) * 4));
-    MGX_HIP_TRY(mgx_hip_malloc(&m->big_rows, (m->n_big > 0 ? m->n_big : 1) * 4));
-    // empty vectors have a null data(): copy only when non-empty
-    if (m->n_small > 0)
-      MGX_HIP_TRY(hipMemcpyAsync(m->small_rows, sm.data(), m->n_small * 4,
-                                 hipMemcpyHostToDevice, ctx->stream));
-    if (m->n_big > 0)
-      MGX_HIP_TRY(hipMemcpyAsync(m->big_rows, bg.data(), m->n_big * 4,
-                                 hipMemcpyHostToDevice, ctx->stream));
+    MGX_TRY(mgx_upload_i32(m->own, sm, &m->small_rows));
+    MGX_TRY(mgx_upload_i32(m->own, bg, &m->big_rows));
     MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
   }
   return MGX_OK;
@@ -536,7 +457,7 @@ extern "C" int mgx_konline_initialized(void) {
 
 extern "C" mgx_status mgx_konline_reset(mgx_context *ctx) {
   (void)ctx;
-  kon_free_state();
+  g_k = KOnState{};
   return MGX_OK;
 }
 
@@ -551,14 +472,14 @@ extern "C" mgx_status mgx_konline_set(mgx_context *ctx, mgx_graph *g,
     return MGX_ERR_INVALID_ARGUMENT;
   }
   MGX_HIP_TRY(hipSetDevice(ctx->device));
-  kon_free_state();
+  g_k = KOnState{};
   g_k.alpha = alpha;
   g_k.eps = epsilon;
   g_k.initialized = true;
   const int64_t V = g ? g->n_vertices : 0;
-  KMaps m;
-  MGX_TRY(kon_build_maps(ctx, g, dense_to_mg, /*create=*/true, &m, nullptr));
-  for (int64_t v = 0; v < V; ++v) g_k.alive_h[m.d2s_h[v]] = 1;
+  KMaps m(ctx);
+  MGX_TRY(kon_build_maps(g, dense_to_mg, &m));
+  for (int64_t v = 0; v < V; ++v) g_k.slots.alive[m.d2s_h[v]] = 1;
   MGX_TRY(kon_grow_slots(ctx, V > 0 ? V : 1));
   // Init (:30-47): centralities[0]=0, omegas[0]=1, lr=ur=0
   MGX_TRY(kon_add_iteration(ctx, 1.0));  // omega[0]=1, cent[0]=0
@@ -580,22 +501,15 @@ extern "C" mgx_status mgx_konline_get(mgx_context *ctx, const int64_t *dense_to_
   // IsInconsistent (:322-338): both directions (graph ⊆ state, state ⊆ graph)
   bool ok = true;
   int64_t n_alive = 0;
-  for (auto a : g_k.alive_h)
+  for (auto a : g_k.slots.alive)
     if (a) ++n_alive;
+  KMaps m(ctx);
+  m.V = V;
+  g_k.slots.map_dense(dense_to_mg, V, /*create=*/false, &m.d2s_h, &ok);
   if (n_alive != V) ok = false;
-  std::vector<int32_t> d2s(V > 0 ? V : 1, -1);
-  for (int64_t v = 0; v < V && ok; ++v) {
-    auto it = g_k.mg2slot.find(dense_to_mg[v]);
-    if (it == g_k.mg2slot.end() || !g_k.alive_h[it->second]) ok = false;
-    else d2s[v] = it->second;
-  }
   if (consistent) *consistent = ok ? 1 : 0;
   if (!ok || !out || V == 0) return MGX_OK;
-  KMaps m;
-  m.V = V;
-  MGX_HIP_TRY(mgx_hip_malloc(&m.dense2slot, V * 4));
-  MGX_HIP_TRY(hipMemcpyAsync(m.dense2slot, d2s.data(), V * 4, hipMemcpyHostToDevice,
-                             ctx->stream));
+  MGX_TRY(mgx_upload_i32(m.own, m.d2s_h, &m.dense2slot));
   return kon_output(ctx, m, out);
 }
 
@@ -621,27 +535,29 @@ extern "C" mgx_status mgx_konline_update(mgx_context *ctx, mgx_graph *g,
 
   // new vertices get slots + history entries (:399-404)
   for (int64_t i = 0; i < n_cv; ++i) {
-    const int32_t s = kon_slot(created_v[i]);
-    g_k.alive_h[s] = 1;
+    const int32_t s = g_k.slots.slot_of(created_v[i], 0);
+    g_k.slots.alive[s] = 1;
   }
-  MGX_TRY(kon_grow_slots(ctx, (int64_t)g_k.slot2mg.size()));
+  MGX_TRY(kon_grow_slots(ctx, g_k.slots.size()));
   // omega[0][new]=1 / cent[i][new]=0: kon_grow_slots fills growth with
   // exactly those defaults, so nothing to write unless the slot existed
   // before (revival) — handle revival explicitly:
   // (cheap: n_cv writes)
   for (int64_t i = 0; i < n_cv; ++i) {
-    const int32_t s = g_k.mg2slot.at(created_v[i]);
+    const int32_t s = g_k.slots.find(created_v[i]);
     const double one = 1.0, zero = 0.0;
     MGX_HIP_TRY(hipMemcpyAsync(g_k.omega[0] + s, &one, 8, hipMemcpyHostToDevice,
                                ctx->stream));
-    for (auto c : g_k.cent)
+    for (auto &c : g_k.cent)
       MGX_HIP_TRY(hipMemcpyAsync(c + s, &zero, 8, hipMemcpyHostToDevice, ctx->stream));
     MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
   }
 
-  KMaps m;
-  MGX_TRY(kon_build_maps(ctx, g, dense_to_mg, /*create=*/true, &m, nullptr));
-  for (int64_t v = 0; v < V; ++v) g_k.alive_h[m.d2s_h[v]] = 1;
+  KMaps m(ctx);
+  MGX_TRY(kon_build_maps(g, dense_to_mg, &m));
+  for (int64_t v = 0; v < V; ++v) g_k.slots.alive[m.d2s_h[v]] = 1;
+  // a vertex of the graph that created_v did not announce got its slot just now
+  MGX_TRY(kon_grow_slots(ctx, g_k.slots.size()));
 
   const double dm = (double)kon_max_degree_dense(ctx, g);
   const double gamma = dm / (1.0 - (g_k.alpha * dm));  // :396 — a, not a^2
@@ -694,41 +610,33 @@ extern "C" mgx_status mgx_konline_update(mgx_context *ctx, mgx_graph *g,
     // edge term slot arrays
     std::vector<int32_t> new_ws, new_vs, del_ws, del_vs;
     for (int64_t i = 0; i < n_ce; ++i) {
-      auto w = g_k.mg2slot.find(created_e[2 * i]);
-      auto v = g_k.mg2slot.find(created_e[2 * i + 1]);
-      if (w == g_k.mg2slot.end() || v == g_k.mg2slot.end()) continue;
-      new_ws.push_back(w->second);
-      new_vs.push_back(v->second);
+      const int32_t w = g_k.slots.find(created_e[2 * i]);
+      const int32_t v = g_k.slots.find(created_e[2 * i + 1]);
+      if (w < 0 || v < 0) continue;
+      new_ws.push_back(w);
+      new_vs.push_back(v);
     }
     for (int64_t i = 0; i < n_de; ++i) {
-      auto w = g_k.mg2slot.find(deleted_e[2 * i]);
-      auto v = g_k.mg2slot.find(deleted_e[2 * i + 1]);
-      if (w == g_k.mg2slot.end() || v == g_k.mg2slot.end()) continue;
-      del_ws.push_back(w->second);
-      del_vs.push_back(v->second);
+      const int32_t w = g_k.slots.find(deleted_e[2 * i]);
+      const int32_t v = g_k.slots.find(deleted_e[2 * i + 1]);
+      if (w < 0 || v < 0) continue;
+      del_ws.push_back(w);
+      del_vs.push_back(v);
     }
-    auto upload_i32 = [&](mgx_scope &own, const std::vector<int32_t> &v,
-                          int32_t **d) -> mgx_status {
-      MGX_TRY(own.alloc_plain(d, (int64_t)v.size()));
-      if (!v.empty())
-        MGX_HIP_TRY(hipMemcpyAsync(*d, v.data(), v.size() * 4, hipMemcpyHostToDevice,
-                                   ctx->stream));
-      return MGX_OK;
-    };
     int32_t *d_new_ws = nullptr, *d_new_vs = nullptr, *d_del_ws = nullptr,
             *d_del_vs = nullptr;
-    MGX_TRY(upload_i32(bufs, new_ws, &d_new_ws));
-    MGX_TRY(upload_i32(bufs, new_vs, &d_new_vs));
-    MGX_TRY(upload_i32(bufs, del_ws, &d_del_ws));
-    MGX_TRY(upload_i32(bufs, del_vs, &d_del_vs));
+    MGX_TRY(mgx_upload_i32(bufs, new_ws, &d_new_ws));
+    MGX_TRY(mgx_upload_i32(bufs, new_vs, &d_new_vs));
+    MGX_TRY(mgx_upload_i32(bufs, del_ws, &d_del_ws));
+    MGX_TRY(mgx_upload_i32(bufs, del_vs, &d_del_vs));
 
     // context_new omegas: new_omega[0] = 1 for all current nodes; levels
     // 1..iteration computed below. Keep as separate device arrays.
     std::vector<double *> new_omega(g_k.iteration + 1, nullptr);
     for (int64_t i = 0; i <= g_k.iteration; ++i)
-      MGX_TRY(bufs.alloc_plain(&new_omega[i], g_k.slots_cap));
-    hipLaunchKernelGGL(mgx_k_fill<double>, dim3((uint32_t)grid_for(g_k.slots_cap)),
-                       dim3(kBlock), 0, ctx->stream, g_k.slots_cap, 1.0, new_omega[0]);
+      MGX_TRY(bufs.alloc_plain(&new_omega[i], g_k.slots_cap()));
+    hipLaunchKernelGGL(mgx_k_fill<double>, dim3((uint32_t)grid_for(g_k.slots_cap())),
+                       dim3(kBlock), 0, ctx->stream, g_k.slots_cap(), 1.0, new_omega[0]);
 
     // updated/frontier state in dense space
     uint32_t *d_updated = nullptr;
@@ -751,7 +659,7 @@ extern "C" mgx_status mgx_konline_update(mgx_context *ctx, mgx_graph *g,
 
     for (int64_t lvl = 1; lvl <= g_k.iteration; ++lvl) {
       // new_omega[lvl] = old omega[lvl] (:266-268; only current slots matter)
-      MGX_HIP_TRY(hipMemcpyAsync(new_omega[lvl], g_k.omega[lvl], g_k.slots_cap * 8,
+      MGX_HIP_TRY(hipMemcpyAsync(new_omega[lvl], g_k.omega[lvl], g_k.slots_cap() * 8,
                                  hipMemcpyDeviceToDevice, ctx->stream));
       MGX_HIP_TRY(hipMemcpyAsync(d_updated, upd_h.data(), V * 4,
                                  hipMemcpyHostToDevice, ctx->stream));
@@ -814,7 +722,7 @@ extern "C" mgx_status mgx_konline_update(mgx_context *ctx, mgx_graph *g,
       for (auto v : front_h) upd_slots.push_back(m.d2s_h[v]);
       mgx_scope slot_bufs(ctx);
       int32_t *d_upd_slots = nullptr;
-      MGX_TRY(upload_i32(slot_bufs, upd_slots, &d_upd_slots));
+      MGX_TRY(mgx_upload_i32(slot_bufs, upd_slots, &d_upd_slots));
       hipLaunchKernelGGL(k_cent_level, dim3((uint32_t)grid_for((int64_t)upd_slots.size())),
                          dim3(kBlock), 0, ctx->stream, (int64_t)upd_slots.size(),
                          d_upd_slots, lvl, pow(g_k.alpha, (double)lvl), new_omega[lvl],
@@ -824,7 +732,7 @@ extern "C" mgx_status mgx_konline_update(mgx_context *ctx, mgx_graph *g,
 
     // merge new omegas into state (:427-431)
     for (int64_t lvl = 1; lvl <= g_k.iteration; ++lvl) {
-      MGX_HIP_TRY(hipMemcpyAsync(g_k.omega[lvl], new_omega[lvl], g_k.slots_cap * 8,
+      MGX_HIP_TRY(hipMemcpyAsync(g_k.omega[lvl], new_omega[lvl], g_k.slots_cap() * 8,
                                  hipMemcpyDeviceToDevice, ctx->stream));
     }
     MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -835,7 +743,7 @@ extern "C" mgx_status mgx_konline_update(mgx_context *ctx, mgx_graph *g,
       for (auto v : front_h) upd_slots.push_back(m.d2s_h[v]);
       mgx_scope slot_bufs(ctx);
       int32_t *d_upd_slots = nullptr;
-      MGX_TRY(upload_i32(slot_bufs, upd_slots, &d_upd_slots));
+      MGX_TRY(mgx_upload_i32(slot_bufs, upd_slots, &d_upd_slots));
       hipLaunchKernelGGL(k_bounds_refresh,
                          dim3((uint32_t)grid_for((int64_t)upd_slots.size())), dim3(kBlock),
                          0, ctx->stream, (int64_t)upd_slots.size(), d_upd_slots,
@@ -846,10 +754,10 @@ extern "C" mgx_status mgx_konline_update(mgx_context *ctx, mgx_graph *g,
 
     // re-activation (:442-455): min lr over active, then ur >= min_lr - eps
     {
-      std::vector<double> lr_h(g_k.slots_cap), ur_h(g_k.slots_cap);
-      MGX_HIP_TRY(hipMemcpyAsync(lr_h.data(), g_k.lr, g_k.slots_cap * 8,
+      std::vector<double> lr_h(g_k.slots_cap()), ur_h(g_k.slots_cap());
+      MGX_HIP_TRY(hipMemcpyAsync(lr_h.data(), g_k.lr, g_k.slots_cap() * 8,
                                  hipMemcpyDeviceToHost, ctx->stream));
-      MGX_HIP_TRY(hipMemcpyAsync(ur_h.data(), g_k.ur, g_k.slots_cap * 8,
+      MGX_HIP_TRY(hipMemcpyAsync(ur_h.data(), g_k.ur, g_k.slots_cap() * 8,
                                  hipMemcpyDeviceToHost, ctx->stream));
       MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
       double min_lr = 1e300;
@@ -862,10 +770,10 @@ extern "C" mgx_status mgx_konline_update(mgx_context *ctx, mgx_graph *g,
     }
     // deleted vertices (:458-464)
     for (int64_t i = 0; i < n_dv; ++i) {
-      auto it = g_k.mg2slot.find(deleted_v[i]);
-      if (it == g_k.mg2slot.end()) continue;
-      g_k.alive_h[it->second] = 0;
-      g_k.active_h[it->second] = 0;
+      const int32_t s = g_k.slots.find(deleted_v[i]);
+      if (s < 0) continue;
+      g_k.slots.alive[s] = 0;
+      g_k.active_h[s] = 0;
     }
   }
 

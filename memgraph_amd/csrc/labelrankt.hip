@@ -44,25 +44,23 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "mgx_device.h"
+#include "mgx_online.h"
 
 namespace {
 
 struct LrtState {
-  std::unordered_map<int64_t, int32_t> mg2slot;
-  std::vector<int64_t> slot2mg;
-  std::vector<uint8_t> alive_h;  // node has label state
+  mgx_slot_table slots;  // alive: node has label state
 
   // device label distributions: pool of (label slot, P) with per-slot
   // segment [off[s], off[s]+len[s])
-  int32_t *lab = nullptr;
-  double *p = nullptr;
-  uint64_t *off = nullptr;  // [slots_cap]
-  uint32_t *len = nullptr;  // [slots_cap]
-  int64_t pool_used = 0, pool_cap = 0;
-  double *sum_w = nullptr;       // [slots_cap]
-  uint32_t *times_upd = nullptr; // [slots_cap]
-  int64_t slots_cap = 0;
+  mgx_dev_array<int32_t> lab;
+  mgx_dev_array<double> p;
+  int64_t pool_used = 0;
+  mgx_dev_array<uint64_t> off;        // per slot
+  mgx_dev_array<uint32_t> len;        // per slot
+  mgx_dev_array<double> sum_w;        // per slot
+  mgx_dev_array<uint32_t> times_upd;  // per slot
+  int64_t slots_cap() const { return std::min({off.cap, len.cap, sum_w.cap, times_upd.cap}); }
 
   // parameters (SetLabels :311-328)
   bool directed = false, weighted = false;
@@ -71,7 +69,7 @@ struct LrtState {
   bool calculated = false;
 };
 
-LrtState g_l;
+LrtState &g_l = *new LrtState;  // never deleted: see mgx_online.h
 
 // ---- kernels -------------------------------------------------------------
 
@@ -379,62 +377,11 @@ __global__ void k_argmax(int64_t n_slots, const int32_t *lab, const double *p,
 
 namespace {
 
-void lrt_free() {
-  if (g_l.lab) (void)hipFree(g_l.lab);
-  if (g_l.p) (void)hipFree(g_l.p);
-  if (g_l.off) (void)hipFree(g_l.off);
-  if (g_l.len) (void)hipFree(g_l.len);
-  if (g_l.sum_w) (void)hipFree(g_l.sum_w);
-  if (g_l.times_upd) (void)hipFree(g_l.times_upd);
-  g_l = LrtState{};
-}
-
-int32_t lrt_slot(int64_t mg) {
-  auto it = g_l.mg2slot.find(mg);
-  if (it != g_l.mg2slot.end()) return it->second;
-  const int32_t s = (int32_t)g_l.slot2mg.size();
-  g_l.mg2slot.emplace(mg, s);
-  g_l.slot2mg.push_back(mg);
-  g_l.alive_h.push_back(0);
-  return s;
-}
-
 mgx_status lrt_grow_slots(mgx_context *ctx, int64_t need) {
-  if (need <= g_l.slots_cap) return MGX_OK;
-  int64_t cap = g_l.slots_cap > 0 ? g_l.slots_cap : 256;
-  while (cap < need) cap *= 2;
-  uint64_t *noff = nullptr;
-  uint32_t *nlen = nullptr, *ntu = nullptr;
-  double *nsw = nullptr;
-  mgx_scope grown(ctx);
-  MGX_TRY(grown.alloc_plain(&noff, cap));
-  MGX_TRY(grown.alloc_plain(&nlen, cap));
-  MGX_TRY(grown.alloc_plain(&ntu, cap));
-  MGX_TRY(grown.alloc_plain(&nsw, cap));
-  MGX_HIP_TRY(hipMemsetAsync(nlen, 0, cap * 4, ctx->stream));
-  MGX_HIP_TRY(hipMemsetAsync(ntu, 0, cap * 4, ctx->stream));
-  MGX_HIP_TRY(hipMemsetAsync(noff, 0, cap * 8, ctx->stream));
-  if (g_l.slots_cap > 0) {
-    MGX_HIP_TRY(hipMemcpyAsync(noff, g_l.off, g_l.slots_cap * 8,
-                               hipMemcpyDeviceToDevice, ctx->stream));
-    MGX_HIP_TRY(hipMemcpyAsync(nlen, g_l.len, g_l.slots_cap * 4,
-                               hipMemcpyDeviceToDevice, ctx->stream));
-    MGX_HIP_TRY(hipMemcpyAsync(ntu, g_l.times_upd, g_l.slots_cap * 4,
-                               hipMemcpyDeviceToDevice, ctx->stream));
-    MGX_HIP_TRY(hipMemcpyAsync(nsw, g_l.sum_w, g_l.slots_cap * 8,
-                               hipMemcpyDeviceToDevice, ctx->stream));
-  }
-  MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  if (g_l.off) (void)hipFree(g_l.off);
-  if (g_l.len) (void)hipFree(g_l.len);
-  if (g_l.times_upd) (void)hipFree(g_l.times_upd);
-  if (g_l.sum_w) (void)hipFree(g_l.sum_w);
-  g_l.off = grown.give_up(noff);
-  g_l.len = grown.give_up(nlen);
-  g_l.times_upd = grown.give_up(ntu);
-  g_l.sum_w = grown.give_up(nsw);
-  g_l.slots_cap = cap;
-  return MGX_OK;
+  MGX_TRY(g_l.off.ensure(ctx, need, 256, g_l.off.cap, mgx_fill_zero(ctx)));
+  MGX_TRY(g_l.len.ensure(ctx, need, 256, g_l.len.cap, mgx_fill_zero(ctx)));
+  MGX_TRY(g_l.times_upd.ensure(ctx, need, 256, g_l.times_upd.cap, mgx_fill_zero(ctx)));
+  return g_l.sum_w.ensure(ctx, need, 256, g_l.sum_w.cap, mgx_fill_none());
 }
 
 // Exclusive scan of u32 into u64 offsets (host round-trip is fine at these
@@ -458,23 +405,19 @@ mgx_status scan_counts_u64(mgx_context *ctx, const uint32_t *d_counts, int64_t n
 }
 
 struct LrtMaps {
+  mgx_scope own;  // of dense2slot
   int32_t *dense2slot = nullptr;
   std::vector<int32_t> d2s_h;
   int64_t V = 0;
-  ~LrtMaps() {
-    if (dense2slot) (void)hipFree(dense2slot);
-  }
+  explicit LrtMaps(mgx_context *ctx) : own(ctx) {}
 };
 
-mgx_status lrt_build_maps(mgx_context *ctx, int64_t V, const int64_t *dense_to_mg,
-                          LrtMaps *m) {
+mgx_status lrt_build_maps(int64_t V, const int64_t *dense_to_mg, LrtMaps *m) {
+  mgx_context *ctx = m->own.ctx;
   m->V = V;
-  m->d2s_h.assign(V > 0 ? V : 1, -1);
-  for (int64_t v = 0; v < V; ++v) m->d2s_h[v] = lrt_slot(dense_to_mg[v]);
-  MGX_TRY(lrt_grow_slots(ctx, (int64_t)g_l.slot2mg.size()));
-  MGX_HIP_TRY(mgx_hip_malloc(&m->dense2slot, (V > 0 ? V : 1) * 4));
-  MGX_HIP_TRY(hipMemcpyAsync(m->dense2slot, m->d2s_h.data(), (V > 0 ? V : 1) * 4,
-                             hipMemcpyHostToDevice, ctx->stream));
+  g_l.slots.map_dense(dense_to_mg, V, /*create=*/true, &m->d2s_h, nullptr);
+  MGX_TRY(lrt_grow_slots(ctx, g_l.slots.size()));
+  MGX_TRY(mgx_upload_i32(m->own, m->d2s_h, &m->dense2slot));
   MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
   return MGX_OK;
 }
@@ -502,27 +445,8 @@ mgx_status lrt_set_structures(mgx_context *ctx, mgx_graph *g, const LrtMaps &m,
   MGX_TRY(scan_counts_u64(ctx, d_counts, n, &seg_off, &total));
   // append region
   const int64_t need = g_l.pool_used + (int64_t)total;
-  if (need > g_l.pool_cap) {
-    int64_t cap = g_l.pool_cap > 0 ? g_l.pool_cap : 4096;
-    while (cap < need) cap *= 2;
-    int32_t *nl = nullptr;
-    double *np = nullptr;
-    mgx_scope grown(ctx);
-    MGX_TRY(grown.alloc_plain(&nl, cap));
-    MGX_TRY(grown.alloc_plain(&np, cap));
-    if (g_l.pool_used > 0) {
-      MGX_HIP_TRY(hipMemcpyAsync(nl, g_l.lab, g_l.pool_used * 4,
-                                 hipMemcpyDeviceToDevice, ctx->stream));
-      MGX_HIP_TRY(hipMemcpyAsync(np, g_l.p, g_l.pool_used * 8, hipMemcpyDeviceToDevice,
-                                 ctx->stream));
-    }
-    MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (g_l.lab) (void)hipFree(g_l.lab);
-    if (g_l.p) (void)hipFree(g_l.p);
-    g_l.lab = grown.give_up(nl);
-    g_l.p = grown.give_up(np);
-    g_l.pool_cap = cap;
-  }
+  MGX_TRY(g_l.lab.ensure(ctx, need, 4096, g_l.pool_used, mgx_fill_none()));
+  MGX_TRY(g_l.p.ensure(ctx, need, 4096, g_l.pool_used, mgx_fill_none()));
   for (auto &o : seg_off) o += (uint64_t)g_l.pool_used;
   uint64_t *d_seg = nullptr;
   MGX_TRY(bufs.alloc_plain(&d_seg, n));
@@ -557,7 +481,7 @@ mgx_status lrt_iteration(mgx_context *ctx, const LrtMaps &m, const uint32_t *row
                          const std::vector<int32_t> &candidates, bool *none_updated,
                          uint64_t *most_updates) {
   const int64_t n = (int64_t)candidates.size();
-  const int64_t n_slots = (int64_t)g_l.slot2mg.size();
+  const int64_t n_slots = g_l.slots.size();
   *none_updated = true;
   *most_updates = 0;
   if (n == 0) return MGX_OK;
@@ -704,19 +628,16 @@ mgx_status lrt_iteration(mgx_context *ctx, const LrtMaps &m, const uint32_t *row
   MGX_HIP_TRY(hipMemcpyAsync(g_l.len, d_out_len, n_slots * 4, hipMemcpyDeviceToDevice,
                              ctx->stream));
   MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  (void)hipFree(g_l.lab);
-  (void)hipFree(g_l.p);
-  g_l.lab = bufs.give_up(nlab);
-  g_l.p = bufs.give_up(np);
+  g_l.lab.adopt(bufs, nlab, (int64_t)(total > 0 ? total : 1));
+  g_l.p.adopt(bufs, np, (int64_t)(total > 0 ? total : 1));
   g_l.pool_used = (int64_t)total;
-  g_l.pool_cap = (int64_t)(total > 0 ? total : 1);
   *most_updates = most;
   return MGX_OK;
 }
 
 // AllLabels (:125-150) into out_label (by dense id), renumbered 1..k.
 mgx_status lrt_all_labels(mgx_context *ctx, const LrtMaps &m, int64_t *out_label) {
-  const int64_t n_slots = (int64_t)g_l.slot2mg.size();
+  const int64_t n_slots = g_l.slots.size();
   if (n_slots == 0 || m.V == 0) return MGX_OK;
   std::vector<int64_t> raw(n_slots);
   {
@@ -724,7 +645,7 @@ mgx_status lrt_all_labels(mgx_context *ctx, const LrtMaps &m, int64_t *out_label
     int64_t *d_s2mg = nullptr, *d_raw = nullptr;
     MGX_TRY(bufs.alloc_plain(&d_s2mg, n_slots));
     MGX_TRY(bufs.alloc_plain(&d_raw, n_slots));
-    MGX_HIP_TRY(hipMemcpyAsync(d_s2mg, g_l.slot2mg.data(), n_slots * 8,
+    MGX_HIP_TRY(hipMemcpyAsync(d_s2mg, g_l.slots.slot2mg.data(), n_slots * 8,
                                hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_argmax, dim3((uint32_t)grid_for(n_slots)), dim3(kBlock), 0,
                        ctx->stream, n_slots, g_l.lab, g_l.p, g_l.off, g_l.len, d_s2mg,
@@ -736,13 +657,13 @@ mgx_status lrt_all_labels(mgx_context *ctx, const LrtMaps &m, int64_t *out_label
   // renumber in ascending label-mg-id order (:135-141); only ALIVE slots
   std::set<int64_t> ordered;
   for (int64_t s = 0; s < n_slots; ++s)
-    if (g_l.alive_h[s] && raw[s] >= 0) ordered.insert(raw[s]);
+    if (g_l.slots.alive[s] && raw[s] >= 0) ordered.insert(raw[s]);
   std::unordered_map<int64_t, int64_t> lookup;
   int64_t li = 1;
   for (auto l : ordered) lookup[l] = li++;
   for (int64_t v = 0; v < m.V; ++v) {
     const int32_t s = m.d2s_h[v];
-    out_label[v] = (g_l.alive_h[s] && raw[s] >= 0) ? lookup[raw[s]] : -1;
+    out_label[v] = (g_l.slots.alive[s] && raw[s] >= 0) ? lookup[raw[s]] : -1;
   }
   return MGX_OK;
 }
@@ -764,17 +685,17 @@ mgx_status lrt_calculate(mgx_context *ctx, mgx_graph *g, const LrtMaps &m,
 
   if (incremental) {
     for (auto mg : to_delete_mg) {  // RemoveDeletedNodes (:74-80)
-      auto it = g_l.mg2slot.find(mg);
-      if (it != g_l.mg2slot.end()) g_l.alive_h[it->second] = 0;
+      const int32_t s = g_l.slots.find(mg);
+      if (s >= 0) g_l.slots.alive[s] = 0;
     }
     std::vector<int32_t> changed_dense;
     std::unordered_map<int64_t, int32_t> mg2dense;
-    for (int64_t v = 0; v < m.V; ++v) mg2dense.emplace(g_l.slot2mg[m.d2s_h[v]], (int32_t)v);
+    for (int64_t v = 0; v < m.V; ++v) mg2dense.emplace(g_l.slots.slot2mg[m.d2s_h[v]], (int32_t)v);
     for (auto mg : changed_mg) {
       auto it = mg2dense.find(mg);
       if (it != mg2dense.end()) {
         changed_dense.push_back(it->second);
-        g_l.alive_h[m.d2s_h[it->second]] = 1;
+        g_l.slots.alive[m.d2s_h[it->second]] = 1;
       }
     }
     MGX_TRY(lrt_set_structures(ctx, g, m, changed_dense, row_ptr, col, w));
@@ -789,10 +710,10 @@ mgx_status lrt_calculate(mgx_context *ctx, mgx_graph *g, const LrtMaps &m,
   } else {
     // full recompute (:285-292)
     g_l.pool_used = 0;
-    for (auto &a : g_l.alive_h) a = 0;
-    for (int64_t v = 0; v < m.V; ++v) g_l.alive_h[m.d2s_h[v]] = 1;
-    MGX_HIP_TRY(hipMemsetAsync(g_l.len, 0, g_l.slots_cap * 4, ctx->stream));
-    MGX_HIP_TRY(hipMemsetAsync(g_l.times_upd, 0, g_l.slots_cap * 4, ctx->stream));
+    for (auto &a : g_l.slots.alive) a = 0;
+    for (int64_t v = 0; v < m.V; ++v) g_l.slots.alive[m.d2s_h[v]] = 1;
+    MGX_HIP_TRY(hipMemsetAsync(g_l.len, 0, g_l.slots_cap() * 4, ctx->stream));
+    MGX_HIP_TRY(hipMemsetAsync(g_l.times_upd, 0, g_l.slots_cap() * 4, ctx->stream));
     MGX_TRY(lrt_set_structures(ctx, g, m, nodes_all, row_ptr, col, w));
     for (int64_t it = 0; it < g_l.max_iterations; ++it) {
       bool none = true;
@@ -803,7 +724,7 @@ mgx_status lrt_calculate(mgx_context *ctx, mgx_graph *g, const LrtMaps &m,
   }
   if (persist) g_l.calculated = true;
   // ResetTimesUpdated (:300)
-  MGX_HIP_TRY(hipMemsetAsync(g_l.times_upd, 0, g_l.slots_cap * 4, ctx->stream));
+  MGX_HIP_TRY(hipMemsetAsync(g_l.times_upd, 0, g_l.slots_cap() * 4, ctx->stream));
   MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
   return lrt_all_labels(ctx, m, out_label);
 }
@@ -814,7 +735,7 @@ extern "C" int mgx_lrt_initialized(void) { return g_l.calculated ? 1 : 0; }
 
 extern "C" mgx_status mgx_lrt_reset(mgx_context *ctx) {
   (void)ctx;
-  lrt_free();
+  g_l = LrtState{};
   return MGX_OK;
 }
 
@@ -840,7 +761,7 @@ extern "C" mgx_status mgx_lrt_set(mgx_context *ctx, mgx_graph *g,
                                   int64_t *out_label) {
   MGX_HIP_TRY(hipSetDevice(ctx->device));
   MGX_TRY(lrt_check_graph(g, directed != 0));
-  lrt_free();
+  g_l = LrtState{};
   g_l.directed = directed != 0;
   g_l.weighted = weighted != 0;
   g_l.sim_th = similarity_threshold;
@@ -850,8 +771,8 @@ extern "C" mgx_status mgx_lrt_set(mgx_context *ctx, mgx_graph *g,
   g_l.max_iterations = max_iterations;
   g_l.max_updates = max_updates;
   const int64_t V = g ? g->n_vertices : 0;
-  LrtMaps m;
-  MGX_TRY(lrt_build_maps(ctx, V, dense_to_mg, &m));
+  LrtMaps m(ctx);
+  MGX_TRY(lrt_build_maps(V, dense_to_mg, &m));
   if (V == 0) {
     g_l.calculated = true;
     return MGX_OK;
@@ -864,8 +785,8 @@ extern "C" mgx_status mgx_lrt_get(mgx_context *ctx, mgx_graph *g,
                                   int *ran_set) {
   MGX_HIP_TRY(hipSetDevice(ctx->device));
   const int64_t V = g ? g->n_vertices : 0;
-  LrtMaps m;
-  MGX_TRY(lrt_build_maps(ctx, V, dense_to_mg, &m));
+  LrtMaps m(ctx);
+  MGX_TRY(lrt_build_maps(V, dense_to_mg, &m));
   if (!g_l.calculated) {
     // GetLabels on an uncalculated state: full compute, NOT persisted
     // (:305-309 — persist=false)
@@ -886,8 +807,8 @@ extern "C" mgx_status mgx_lrt_update(mgx_context *ctx, mgx_graph *g,
                                      int64_t *out_label) {
   MGX_HIP_TRY(hipSetDevice(ctx->device));
   const int64_t V = g ? g->n_vertices : 0;
-  LrtMaps m;
-  MGX_TRY(lrt_build_maps(ctx, V, dense_to_mg, &m));
+  LrtMaps m(ctx);
+  MGX_TRY(lrt_build_maps(V, dense_to_mg, &m));
   if (!g_l.calculated) {
     if (V == 0) return MGX_OK;
     return lrt_calculate(ctx, g, m, {}, {}, /*persist=*/false, out_label);

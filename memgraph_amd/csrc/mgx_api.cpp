@@ -150,6 +150,23 @@ extern "C" int64_t mgx_test_scope_hook(int64_t fail_at) {
   return g_scope_outstanding.load();
 }
 
+namespace {
+std::atomic<int64_t> g_state_blocks{0};
+std::atomic<int64_t> g_state_first_cap{-1};
+}  // namespace
+
+extern "C" int64_t mgx_test_state_hook(int64_t first_cap) {
+  g_state_first_cap.store(first_cap > 0 ? first_cap : -1);
+  return g_state_blocks.load();
+}
+
+int64_t mgx_state_first_cap(int64_t site_first_cap) {
+  const int64_t o = g_state_first_cap.load();
+  return o > 0 ? o : site_first_cap;
+}
+
+void mgx_state_blocks_add(int64_t delta) { g_state_blocks += delta; }
+
 mgx_status mgx_scope::take(void **p, size_t bytes, bool cached) {
   if (g_scope_fail_in.load() > 0 && g_scope_fail_in.fetch_sub(1) == 1) {
     g_scope_fail_in.store(-1);

@@ -136,6 +136,14 @@ struct mgx_scope {
 // fail_at-th scope allocation from now on returns MGX_ERR_OUT_OF_MEMORY on
 // the host, before any HIP call; -1 disarms it.
 extern "C" int64_t mgx_test_scope_hook(int64_t fail_at);
+// The same for the persistent arrays of the online modules (mgx_dev_array,
+// mgx_online.h). Returns how many blocks they hold right now, then overrides
+// the first capacity of every growth site: > 0 replaces it, so that a few
+// vertices already make every array grow with live contents; -1 restores the
+// sites' own values.
+extern "C" int64_t mgx_test_state_hook(int64_t first_cap);
+int64_t mgx_state_first_cap(int64_t site_first_cap);  // the override, if one is set
+void mgx_state_blocks_add(int64_t delta);
 
 // Degree bins for the fused sweep kernels. Rows are classified by degree;
 // within a bin rows are in ascending id order (stable 2-bit radix sort) so

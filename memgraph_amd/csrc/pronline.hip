@@ -32,37 +32,33 @@
 //    each fully parallel over affected walks.
 //  - Walk length is capped at 1<<20 steps (P(hit) < eps*(1-eps)^1e6 ~ 0).
 
+#include <algorithm>
 #include <unordered_map>
 #include <vector>
 
 #include "../../include/mgx_graphgen.h"
-#include "mgx_device.h"
+#include "mgx_online.h"
 
 namespace {
 
 constexpr uint32_t kMaxSteps = 1u << 20;
 
 struct PrOnlineState {
-  // host slot map: memgraph id -> slot (stable across graph changes)
-  std::unordered_map<int64_t, int32_t> mg2slot;
-  std::vector<int64_t> slot2mg;
-  std::vector<uint8_t> slot_alive_h;
+  mgx_slot_table slots;  // memgraph id -> slot (stable across graph changes)
 
   // device
-  uint32_t *e_walk = nullptr;
-  uint32_t *e_pos = nullptr;
-  int32_t *e_node = nullptr;  // slot id; -1 = dead entry
-  int64_t pool_cap = 0;
-  unsigned long long *d_cursor = nullptr;  // [0]=append cursor, [1]=overflow
-  int64_t pool_used = 0;                   // host mirror (valid after sync)
+  mgx_dev_array<uint32_t> e_walk, e_pos;
+  mgx_dev_array<int32_t> e_node;  // slot id; -1 = dead entry
+  mgx_dev_array<unsigned long long> d_cursor;  // [0]=append cursor, [1]=overflow
+  int64_t pool_used = 0;                       // host mirror (valid after sync)
+  int64_t pool_cap() const { return std::min({e_walk.cap, e_pos.cap, e_node.cap}); }
 
-  int32_t *w_start = nullptr;  // slot
-  uint32_t *w_gen = nullptr;   // regeneration counter (RNG stream)
-  uint8_t *w_dead = nullptr;
-  int64_t n_walks = 0, walks_cap = 0;
+  mgx_dev_array<int32_t> w_start;  // slot
+  mgx_dev_array<uint32_t> w_gen;   // regeneration counter (RNG stream)
+  mgx_dev_array<uint8_t> w_dead;
+  int64_t n_walks = 0;
 
-  uint8_t *d_slot_alive = nullptr;
-  int64_t slots_cap_dev = 0;
+  mgx_dev_array<uint8_t> d_slot_alive;
 
   uint64_t seed_mixed = 0;
   int64_t R = 10;
@@ -70,7 +66,7 @@ struct PrOnlineState {
   bool initialized = false;
 };
 
-PrOnlineState g_st;
+PrOnlineState &g_st = *new PrOnlineState;  // never deleted: see mgx_online.h
 
 // ---- kernels -------------------------------------------------------------
 
@@ -238,149 +234,49 @@ __global__ void k_rank_out(int64_t V, const int32_t *dense2slot, const uint32_t 
 // ---- host helpers --------------------------------------------------------
 
 mgx_status ensure_pool(mgx_context *ctx, int64_t need_cap) {
-  if (need_cap <= g_st.pool_cap) return MGX_OK;
-  int64_t cap = g_st.pool_cap > 0 ? g_st.pool_cap : (1 << 20);
-  while (cap < need_cap) cap *= 2;
-  uint32_t *nw = nullptr, *np = nullptr;
-  int32_t *nn = nullptr;
-  mgx_scope grown(ctx);
-  MGX_TRY(grown.alloc_plain(&nw, cap));
-  MGX_TRY(grown.alloc_plain(&np, cap));
-  MGX_TRY(grown.alloc_plain(&nn, cap));
-  if (g_st.pool_used > 0) {
-    MGX_HIP_TRY(hipMemcpyAsync(nw, g_st.e_walk, g_st.pool_used * 4,
-                               hipMemcpyDeviceToDevice, ctx->stream));
-    MGX_HIP_TRY(hipMemcpyAsync(np, g_st.e_pos, g_st.pool_used * 4,
-                               hipMemcpyDeviceToDevice, ctx->stream));
-    MGX_HIP_TRY(hipMemcpyAsync(nn, g_st.e_node, g_st.pool_used * 4,
-                               hipMemcpyDeviceToDevice, ctx->stream));
-    MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  }
-  if (g_st.e_walk) (void)hipFree(g_st.e_walk);
-  if (g_st.e_pos) (void)hipFree(g_st.e_pos);
-  if (g_st.e_node) (void)hipFree(g_st.e_node);
-  g_st.e_walk = grown.give_up(nw);
-  g_st.e_pos = grown.give_up(np);
-  g_st.e_node = grown.give_up(nn);
-  g_st.pool_cap = cap;
-  return MGX_OK;
+  MGX_TRY(g_st.e_walk.ensure(ctx, need_cap, 1 << 20, g_st.pool_used, mgx_fill_none()));
+  MGX_TRY(g_st.e_pos.ensure(ctx, need_cap, 1 << 20, g_st.pool_used, mgx_fill_none()));
+  return g_st.e_node.ensure(ctx, need_cap, 1 << 20, g_st.pool_used, mgx_fill_none());
 }
 
 mgx_status ensure_walks(mgx_context *ctx, int64_t need) {
-  if (need <= g_st.walks_cap) return MGX_OK;
-  int64_t cap = g_st.walks_cap > 0 ? g_st.walks_cap : (1 << 16);
-  while (cap < need) cap *= 2;
-  int32_t *ns = nullptr;
-  uint32_t *ng = nullptr;
-  uint8_t *nd = nullptr;
-  mgx_scope grown(ctx);
-  MGX_TRY(grown.alloc_plain(&ns, cap));
-  MGX_TRY(grown.alloc_plain(&ng, cap));
-  MGX_TRY(grown.alloc_plain(&nd, cap));
-  MGX_HIP_TRY(hipMemsetAsync(ng, 0, cap * 4, ctx->stream));
-  MGX_HIP_TRY(hipMemsetAsync(nd, 0, cap, ctx->stream));
-  if (g_st.n_walks > 0) {
-    MGX_HIP_TRY(hipMemcpyAsync(ns, g_st.w_start, g_st.n_walks * 4,
-                               hipMemcpyDeviceToDevice, ctx->stream));
-    MGX_HIP_TRY(hipMemcpyAsync(ng, g_st.w_gen, g_st.n_walks * 4,
-                               hipMemcpyDeviceToDevice, ctx->stream));
-    MGX_HIP_TRY(hipMemcpyAsync(nd, g_st.w_dead, g_st.n_walks,
-                               hipMemcpyDeviceToDevice, ctx->stream));
-  }
-  MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  if (g_st.w_start) (void)hipFree(g_st.w_start);
-  if (g_st.w_gen) (void)hipFree(g_st.w_gen);
-  if (g_st.w_dead) (void)hipFree(g_st.w_dead);
-  g_st.w_start = grown.give_up(ns);
-  g_st.w_gen = grown.give_up(ng);
-  g_st.w_dead = grown.give_up(nd);
-  g_st.walks_cap = cap;
-  return MGX_OK;
+  MGX_TRY(g_st.w_start.ensure(ctx, need, 1 << 16, g_st.n_walks, mgx_fill_none()));
+  MGX_TRY(g_st.w_gen.ensure(ctx, need, 1 << 16, g_st.n_walks, mgx_fill_zero(ctx)));
+  return g_st.w_dead.ensure(ctx, need, 1 << 16, g_st.n_walks, mgx_fill_zero(ctx));
 }
 
 mgx_status sync_slot_alive(mgx_context *ctx) {
-  const int64_t n = (int64_t)g_st.slot_alive_h.size();
-  if (n > g_st.slots_cap_dev) {
-    if (g_st.d_slot_alive) (void)hipFree(g_st.d_slot_alive);
-    int64_t cap = 64;
-    while (cap < n) cap *= 2;
-    MGX_HIP_TRY(mgx_hip_malloc(&g_st.d_slot_alive, cap));
-    g_st.slots_cap_dev = cap;
-  }
+  const int64_t n = g_st.slots.size();
+  MGX_TRY(g_st.d_slot_alive.ensure(ctx, n, 64, 0, mgx_fill_none()));
   if (n > 0) {
-    MGX_HIP_TRY(hipMemcpyAsync(g_st.d_slot_alive, g_st.slot_alive_h.data(), n,
+    MGX_HIP_TRY(hipMemcpyAsync(g_st.d_slot_alive, g_st.slots.alive.data(), n,
                                hipMemcpyHostToDevice, ctx->stream));
   }
   return MGX_OK;
 }
 
-void free_state() {
-  if (g_st.e_walk) (void)hipFree(g_st.e_walk);
-  if (g_st.e_pos) (void)hipFree(g_st.e_pos);
-  if (g_st.e_node) (void)hipFree(g_st.e_node);
-  if (g_st.w_start) (void)hipFree(g_st.w_start);
-  if (g_st.w_gen) (void)hipFree(g_st.w_gen);
-  if (g_st.w_dead) (void)hipFree(g_st.w_dead);
-  if (g_st.d_cursor) (void)hipFree(g_st.d_cursor);
-  if (g_st.d_slot_alive) (void)hipFree(g_st.d_slot_alive);
-  g_st = PrOnlineState{};
-}
-
-// Slot of mg id, creating if absent.
-int32_t slot_of(int64_t mg_id) {
-  auto it = g_st.mg2slot.find(mg_id);
-  if (it != g_st.mg2slot.end()) return it->second;
-  const int32_t s = (int32_t)g_st.slot2mg.size();
-  g_st.mg2slot.emplace(mg_id, s);
-  g_st.slot2mg.push_back(mg_id);
-  g_st.slot_alive_h.push_back(1);
-  return s;
-}
-
 struct Maps {
+  mgx_scope own;                  // of the two device maps
   int32_t *slot2dense = nullptr;  // device
   int32_t *dense2slot = nullptr;  // device
   int64_t V = 0;
-  mgx_context *ctx = nullptr;
-  ~Maps() {
-    if (slot2dense) (void)hipFree(slot2dense);
-    if (dense2slot) (void)hipFree(dense2slot);
-  }
+  explicit Maps(mgx_context *ctx) : own(ctx) {}
 };
 
 // Build device slot<->dense maps for the current scan; creates slots for
 // any unseen mg ids when `create` (set path), else leaves them unmapped.
-mgx_status build_maps(mgx_context *ctx, const int64_t *dense_to_mg, int64_t V, bool create,
-                      Maps *m, bool *all_known) {
-  m->ctx = ctx;
+mgx_status build_maps(const int64_t *dense_to_mg, int64_t V, bool create, Maps *m,
+                      bool *all_known) {
+  mgx_context *ctx = m->own.ctx;
   m->V = V;
-  std::vector<int32_t> d2s(V > 0 ? V : 1, -1);
-  bool known = true;
-  for (int64_t v = 0; v < V; ++v) {
-    if (create) {
-      d2s[v] = slot_of(dense_to_mg[v]);
-    } else {
-      auto it = g_st.mg2slot.find(dense_to_mg[v]);
-      if (it == g_st.mg2slot.end() || !g_st.slot_alive_h[it->second]) {
-        known = false;
-        d2s[v] = -1;
-      } else {
-        d2s[v] = it->second;
-      }
-    }
-  }
-  const int64_t n_slots = (int64_t)g_st.slot2mg.size();
-  std::vector<int32_t> s2d(n_slots > 0 ? n_slots : 1, -1);
+  std::vector<int32_t> d2s;
+  g_st.slots.map_dense(dense_to_mg, V, create, &d2s, all_known, /*alive_init=*/1);
+  std::vector<int32_t> s2d(g_st.slots.size() > 0 ? g_st.slots.size() : 1, -1);
   for (int64_t v = 0; v < V; ++v)
     if (d2s[v] >= 0) s2d[d2s[v]] = (int32_t)v;
-  MGX_HIP_TRY(mgx_hip_malloc(&m->dense2slot, (V > 0 ? V : 1) * 4));
-  MGX_HIP_TRY(mgx_hip_malloc(&m->slot2dense, (n_slots > 0 ? n_slots : 1) * 4));
-  MGX_HIP_TRY(hipMemcpyAsync(m->dense2slot, d2s.data(), (V > 0 ? V : 1) * 4,
-                             hipMemcpyHostToDevice, ctx->stream));
-  MGX_HIP_TRY(hipMemcpyAsync(m->slot2dense, s2d.data(), (n_slots > 0 ? n_slots : 1) * 4,
-                             hipMemcpyHostToDevice, ctx->stream));
+  MGX_TRY(mgx_upload_i32(m->own, d2s, &m->dense2slot));
+  MGX_TRY(mgx_upload_i32(m->own, s2d, &m->slot2dense));
   MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  if (all_known) *all_known = known;
   return MGX_OK;
 }
 
@@ -391,9 +287,7 @@ mgx_status run_gen(mgx_context *ctx, const Maps &m, mgx_graph *g,
                    const GenItem *d_items, int64_t n_items, double eps,
                    int64_t expected_append) {
   if (n_items == 0) return MGX_OK;
-  if (!g_st.d_cursor) {
-    MGX_HIP_TRY(mgx_hip_malloc(&g_st.d_cursor, 16));
-  }
+  MGX_TRY(g_st.d_cursor.ensure(ctx, 2, 2, 0, mgx_fill_none()));
   uint64_t eps_bits;
   if (eps >= 1.0) {
     eps_bits = ~0ull;
@@ -418,7 +312,7 @@ mgx_status run_gen(mgx_context *ctx, const Maps &m, mgx_graph *g,
     A.e_pos = g_st.e_pos;
     A.e_node = g_st.e_node;
     A.cursor = g_st.d_cursor;
-    A.pool_cap = (uint64_t)g_st.pool_cap;
+    A.pool_cap = (uint64_t)g_st.pool_cap();
     unsigned long long init[2] = {snapshot, 0};
     MGX_HIP_TRY(hipMemcpyAsync(g_st.d_cursor, init, 16, hipMemcpyHostToDevice,
                                ctx->stream));
@@ -427,7 +321,7 @@ mgx_status run_gen(mgx_context *ctx, const Maps &m, mgx_graph *g,
     unsigned long long out[2] = {0, 0};
     MGX_HIP_TRY(hipMemcpyAsync(out, g_st.d_cursor, 16, hipMemcpyDeviceToHost, ctx->stream));
     MGX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (!out[1] && out[0] <= (unsigned long long)g_st.pool_cap) {
+    if (!out[1] && out[0] <= (unsigned long long)g_st.pool_cap()) {
       g_st.pool_used = (int64_t)out[0];
       return MGX_OK;
     }
@@ -439,7 +333,7 @@ mgx_status run_gen(mgx_context *ctx, const Maps &m, mgx_graph *g,
 }
 
 mgx_status compute_rank(mgx_context *ctx, const Maps &m, double *out_rank) {
-  const int64_t n_slots = (int64_t)g_st.slot2mg.size();
+  const int64_t n_slots = g_st.slots.size();
   MGX_TRY(sync_slot_alive(ctx));
   uint32_t *counter = nullptr;
   unsigned long long *d_sum = nullptr;
@@ -548,7 +442,7 @@ extern "C" int mgx_pronline_initialized(void) { return g_st.initialized ? 1 : 0;
 
 extern "C" mgx_status mgx_pronline_reset(mgx_context *ctx) {
   (void)ctx;
-  free_state();
+  g_st = PrOnlineState{};
   return MGX_OK;
 }
 
@@ -560,14 +454,14 @@ extern "C" mgx_status mgx_pronline_set(mgx_context *ctx, mgx_graph *g,
     return MGX_ERR_INVALID_ARGUMENT;
   }
   MGX_HIP_TRY(hipSetDevice(ctx->device));
-  free_state();
+  g_st = PrOnlineState{};
   g_st.R = R > 0 ? R : 1;
   g_st.eps = eps;
   g_st.seed_mixed = mgx_seed_mix(seed);
   g_st.initialized = true;
   const int64_t V = g ? g->n_vertices : 0;  // null graph == empty graph
-  Maps m;
-  MGX_TRY(build_maps(ctx, dense_to_mg, V, /*create=*/true, &m, nullptr));
+  Maps m(ctx);
+  MGX_TRY(build_maps(dense_to_mg, V, /*create=*/true, &m, nullptr));
   std::vector<int32_t> starts(V);
   for (int64_t v = 0; v < V; ++v) starts[v] = (int32_t)v;  // slots == dense here
   MGX_TRY(spawn_walks(ctx, m, g, starts));
@@ -577,9 +471,9 @@ extern "C" mgx_status mgx_pronline_set(mgx_context *ctx, mgx_graph *g,
 extern "C" mgx_status mgx_pronline_get(mgx_context *ctx, const int64_t *dense_to_mg,
                                        int64_t V, double *out_rank, int *consistent) {
   MGX_HIP_TRY(hipSetDevice(ctx->device));
-  Maps m;
+  Maps m(ctx);
   bool known = true;
-  MGX_TRY(build_maps(ctx, dense_to_mg, V, /*create=*/false, &m, &known));
+  MGX_TRY(build_maps(dense_to_mg, V, /*create=*/false, &m, &known));
   if (consistent) *consistent = known ? 1 : 0;
   if (!known) return MGX_OK;
   return compute_rank(ctx, m, out_rank);
@@ -604,11 +498,11 @@ extern "C" mgx_status mgx_pronline_update(mgx_context *ctx, mgx_graph *g,
   // Slots for created vertices must exist before edge rewires reference
   // them; build the maps AFTER creating/reviving slots.
   for (int64_t i = 0; i < n_cv; ++i) {
-    const int32_t s = slot_of(created_v[i]);
-    g_st.slot_alive_h[s] = 1;
+    const int32_t s = g_st.slots.slot_of(created_v[i], 1);
+    g_st.slots.alive[s] = 1;
   }
-  Maps m;
-  MGX_TRY(build_maps(ctx, dense_to_mg, V, /*create=*/false, &m, nullptr));
+  Maps m(ctx);
+  MGX_TRY(build_maps(dense_to_mg, V, /*create=*/false, &m, nullptr));
 
   // Scan membership (mg id -> in current graph) for the NodeExists check
   // (pagerank.cpp:221-223): regrow only if `from` is in the post-change
@@ -619,34 +513,34 @@ extern "C" mgx_status mgx_pronline_update(mgx_context *ctx, mgx_graph *g,
 
   for (int64_t i = 0; i < n_de; ++i) {
     const int64_t from = deleted_e[2 * i];
-    auto it = g_st.mg2slot.find(from);
-    if (it == g_st.mg2slot.end()) continue;
+    const int32_t slot = g_st.slots.find(from);
+    if (slot < 0) continue;
     const bool exists = mg2dense.count(from) > 0;
-    MGX_TRY(rewire_from(ctx, m, g, it->second, exists));
+    MGX_TRY(rewire_from(ctx, m, g, slot, exists));
   }
   for (int64_t i = 0; i < n_dv; ++i) {
-    auto it = g_st.mg2slot.find(deleted_v[i]);
-    if (it == g_st.mg2slot.end()) continue;
-    g_st.slot_alive_h[it->second] = 0;
+    const int32_t slot = g_st.slots.find(deleted_v[i]);
+    if (slot < 0) continue;
+    g_st.slots.alive[slot] = 0;
     if (g_st.n_walks > 0)
       hipLaunchKernelGGL(k_mark_dead_walks, dim3((uint32_t)grid_for(g_st.n_walks)),
                          dim3(kBlock), 0, ctx->stream, g_st.n_walks, g_st.w_start,
-                         it->second, g_st.w_dead);
+                         slot, g_st.w_dead);
   }
   {
     std::vector<int32_t> starts;
     starts.reserve(n_cv);
     for (int64_t i = 0; i < n_cv; ++i) {
-      auto it = g_st.mg2slot.find(created_v[i]);
-      if (it != g_st.mg2slot.end()) starts.push_back(it->second);
+      const int32_t slot = g_st.slots.find(created_v[i]);
+      if (slot >= 0) starts.push_back(slot);
     }
     MGX_TRY(spawn_walks(ctx, m, g, starts));
   }
   for (int64_t i = 0; i < n_ce; ++i) {
     const int64_t from = created_e[2 * i];
-    auto it = g_st.mg2slot.find(from);
-    if (it == g_st.mg2slot.end()) continue;
-    MGX_TRY(rewire_from(ctx, m, g, it->second, mg2dense.count(from) > 0));
+    const int32_t slot = g_st.slots.find(from);
+    if (slot < 0) continue;
+    MGX_TRY(rewire_from(ctx, m, g, slot, mg2dense.count(from) > 0));
   }
   return compute_rank(ctx, m, out_rank);
 }

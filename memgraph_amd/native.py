@@ -134,6 +134,14 @@ class Native:
         self.lib.mgx_test_scope_hook.restype = ctypes.c_int64
         return self.lib.mgx_test_scope_hook(ctypes.c_int64(fail_at))
 
+    def test_state_hook(self, first_cap=-1):
+        """Test support: device blocks the online modules' persistent arrays
+        hold right now, in the whole process. Then makes every such array
+        start at first_cap elements instead of its own first capacity, so that
+        tiny graphs already grow them; -1 restores the arrays' own values."""
+        self.lib.mgx_test_state_hook.restype = ctypes.c_int64
+        return self.lib.mgx_test_state_hook(ctypes.c_int64(first_cap))
+
     # --- graphs ---
     def graph_from_coo(self, ctx, src, dst, n_vertices, weights=None, flags=BUILD_IN_CSR):
         src = np.ascontiguousarray(src, dtype=np.int64)
